@@ -24,13 +24,19 @@ every rank. RPT_BENCH_BACKEND=gloo rehearses N ranks on fewer GPUs (ranks share 
 the C5 section's included, then runs the torch.distributed composition over host memory, reported as
 torch_merge_ms, never as or_merge_ms).
 
-At N > 1 (and with --c5-merge at N = 1) the line also carries `c5_merge`: the north_star's C5 pipeline at
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it builds the filter and the
+probe column, warms up, times the K steps, writes the last step's outputs if `--dump-outputs DIR` is given (see
+dump_outputs) and prints the headline fields (metric, value, unit, ms_per_step, dtype, config, ...). Everything
+else described below (the stream calibration, the timed build, the merge check, the per-kernel second pass with
+`roofline` / `kernels_ms` / `probe_total`, `build`, `c5_merge`, `cpu_baseline`) runs, and is reported, with `--full`.
+
+With --full at N > 1 (and with --c5-merge at N = 1) the line also carries `c5_merge`: the north_star's C5 pipeline at
 this node's N, after the headline is timed: every rank inserts its 1e9-row shard into an 8 GiB filter sized
 for 8e9 rows, rpt_bf_allreduce_or_ws OR-merges the partials over RCCL (xGMI), the merged filter is checked
 bit-identical to a single build of all N * 1e9 rows, and every rank probes its 1e9-row slice against it. The
 record carries each rank's peak device memory over the section (hipMemGetInfo) and the section's wall time.
 
-Prints ONE JSON line on rank 0. `roofline` prices the dominant kernel from HIP events the library
+Prints ONE JSON line on rank 0. With --full, `roofline` prices the dominant kernel from HIP events the library
 records on the launch stream (rpt_profiling_*) and its PMC traffic from profiles/pmc/<config>.json
 (the exact template instantiation, or null); `cpu_baseline` times the C++ restatement (oracle/) on
 rank 0's host cores.
@@ -89,6 +95,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the stream calibration, the timed build, the "
+                         "merge check (N > 1), the per-kernel second pass (roofline, kernels_ms, probe_total), the C5 "
+                         "section and the CPU baseline. Without it the run sets up, warms up, times the steps and "
+                         "prints the headline fields only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float64): "
+                         "sel_summary (survivor count, sum of the selection vector as low / high 32-bit halves) and "
+                         "sel (the selection vector, or a fixed seeded sample of it, see dump_outputs)")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="BASELINE config (sets --build-rows / --filter-rows); default C2")
     ap.add_argument("--probe-rows", type=float, default=1e9, help="probe rows per GPU")
@@ -143,7 +158,10 @@ def parse():
     ap.add_argument("--kernel-events-in-timed-region", action="store_true",
                     help="record the per-kernel HIP events inside the timed steps (r01-r05 arrangement; they cost "
                          "~25 us per step) instead of in an identical second pass of K steps after them")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def stream_calibration(device, nbytes: int = STREAM_CAL_BYTES, reps: int = 5) -> dict:
@@ -407,6 +425,33 @@ def run_c5_merge(args, rank: int, world: int, device, comm, barrier, reduce_max,
     return rec
 
 
+DUMP_SEL_SAMPLE = 4 * 10**6  # selection-vector entries written by --dump-outputs (float64: 32 MB)
+DUMP_SEED = 0x5EED0B5
+
+
+def dump_outputs(out_dir: str, out_sel, survivors: int, suffix: str = "") -> None:
+    """--dump-outputs: what a caller of the timed path (probe_async) received from the last timed step, as float64
+    .npy files (every value is an integer below 2^53, so float64 holds it exactly):
+      sel_summary  [survivor count, sum of the selection vector mod 2^32, that sum >> 32]: covers every entry
+      sel          the ascending uint32 selection vector out_sel[:count]; above DUMP_SEL_SAMPLE entries, its entries
+                   at DUMP_SEL_SAMPLE positions floor(u * count), u drawn once from a generator seeded with DUMP_SEED
+                   (the same positions in every run with the same survivor count) and sorted
+    Inputs are the seeded synthetic key columns, so two builds run with the same arguments write equal files."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    sel = out_sel[:survivors].to(torch.int64) & 0xFFFFFFFF  # the uint32 entries live in an int32 tensor
+    total = int(sel.sum().item())
+    summary = np.array([survivors, total & 0xFFFFFFFF, total >> 32], dtype=np.float64)
+    if survivors > DUMP_SEL_SAMPLE:
+        u = np.sort(np.random.default_rng(DUMP_SEED).random(DUMP_SEL_SAMPLE))
+        pos = np.minimum((u * survivors).astype(np.int64), survivors - 1)
+        sel = sel[torch.from_numpy(pos).to(sel.device)]
+    np.save(os.path.join(out_dir, f"sel_summary{suffix}.npy"), summary)
+    np.save(os.path.join(out_dir, f"sel{suffix}.npy"), sel.cpu().numpy().astype(np.float64))
+
+
 def pmc_traffic(kernel: str, tag: str):
     """HBM bytes per launch of exactly this kernel instantiation in this config, from the PMC summary
     tools/profile_round.sh wrote (profiles/pmc/<tag>.json: FETCH_SIZE doubled per the gfx950 correction +
@@ -593,6 +638,10 @@ def main():
                           args.cpu_lag)
         print(json.dumps({"cpu_baseline": cb, "config": cfg, "key_type": args.key_type}), flush=True)
         return
+    if not args.full:
+        for flag in ("--c5-merge", "--kernel-events-in-timed-region"):
+            if getattr(args, flag[2:].replace("-", "_")):
+                sys.exit(f"bench.py: {flag} asks for a measurement beside the headline; add --full")
     world = int(os.environ.get("WORLD_SIZE", "0"))
     if world == 0:
         if args.gpus > 1:
@@ -658,22 +707,23 @@ def main():
     # ---- what this box streams (untimed, before anything else is resident) ------------------------
     shared_device = backend == "gloo" and world > max(1, torch.cuda.device_count())
     stream_cal = None
-    if not args.no_stream_calibration and not shared_device:
+    if args.full and not args.no_stream_calibration and not shared_device:
         stream_cal = stream_calibration(device)
 
-    # ---- CREATE_BF: sharded build + OR merge (reported, not the headline) -------------------------
+    # ---- CREATE_BF: sharded build + OR merge (timed and reported with --full, not the headline) ----
     lo, hi = shard_range(n_build, rank, world)
     build_keys = keys_of(rpt_amd.synth_build_keys(hi - lo, start=lo, device=device))
     bf = rpt_amd.BloomFilter(n_filter, device=device)
-    bf.insert(build_keys)  # warm-up: workspace allocation, code-object load
+    bf.insert(build_keys)  # the filter now holds this rank's keys (--full: the warm-up of the timed build)
     build_reps = 5
     torch.cuda.synchronize()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(build_reps):  # clear + insert: the filter ends up holding exactly this rank's keys
-        bf.clear()
-        bf.insert(build_keys)
-    torch.cuda.synchronize()
+    if args.full:
+        for _ in range(build_reps):  # clear + insert: the filter ends up holding exactly this rank's keys
+            bf.clear()
+            bf.insert(build_keys)
+        torch.cuda.synchronize()
     t1 = time.perf_counter()
     del build_keys
     # The product merge is rpt_bf_allreduce_or_ws over a library-made RCCL communicator. A failing
@@ -706,7 +756,7 @@ def main():
     merge_ws = None
     bf.finalized = True
     merge_check = None
-    if world > 1 and not args.no_merge_check:
+    if world > 1 and args.full and not args.no_merge_check:
         # untimed: the OR-merged filter must be bit-identical to a single-GPU build of all rows (built
         # here in 1e9-row pieces: inserts into one filter compose)
         ref = rpt_amd.BloomFilter(n_filter, device=device)
@@ -764,17 +814,19 @@ def main():
     barrier()
     elapsed = time.perf_counter() - ts
     rpt_lib.profiling(False)
+    survivors = int(out_count.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_sel, survivors, "" if world == 1 else f"_rank{rank}")
     kernel_events = "inside the timed steps"
-    if not args.kernel_events_in_timed_region:
+    if args.full and not args.kernel_events_in_timed_region:
         kernel_events = "an identical second pass of K steps right after the timed ones (the timed steps run without them)"
         rpt_lib.profiling(True)
         for _ in range(args.steps):
             step()
         torch.cuda.synchronize()
         rpt_lib.profiling(False)
-    ktimes = rpt_lib.kernel_times()
+    ktimes = rpt_lib.kernel_times() if args.full else {}
 
-    survivors = int(out_count.item())
     probe_ms = statistics.mean(e[0].elapsed_time(e[1]) for e in events)
 
     t = torch.tensor([elapsed, (t1 - t0) / build_reps, t2 - t1], dtype=torch.float64,
@@ -788,7 +840,7 @@ def main():
     # composition (the gloo rehearsal on a box with fewer GPUs than ranks, --merge torch), so bench's sharding,
     # merge check, reductions and record assembly run before the driver's multi-GPU run does them.
     c5 = None
-    if (world > 1 and not args.no_c5_merge) or (world == 1 and args.c5_merge):
+    if args.full and ((world > 1 and not args.no_c5_merge) or (world == 1 and args.c5_merge)):
         del keys, out_sel, ws
         torch.cuda.empty_cache()
         c5_comm = comm if comm is not None else (RcclComm.single(device) if world == 1 else None)
@@ -827,22 +879,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * n_probe * args.steps / elapsed
-        probe_bytes = key_bytes * n_probe + SEL_BYTES * survivors
-        # dominant kernel of the step (largest total device time)
-        dom_name, (dom_calls, dom_total) = max(ktimes.items(), key=lambda kv: kv[1][1])
-        dom_ms = dom_total / dom_calls
-        dom_calls_per_step = dom_calls / args.steps
-        dom_bytes = algorithmic_bytes(dom_name, n_probe, survivors, key_bytes) / dom_calls_per_step
-        achieved = dom_bytes / (dom_ms * 1e-3)
-        traffic = pmc_traffic(dom_name, tag)
-        # whole-step HBM traffic: every kernel of the step at its PMC bytes per launch
-        step_traffic, unprofiled = 0.0, []
-        for name, (calls, _total) in ktimes.items():
-            tr = pmc_traffic(name, tag)
-            if tr is None:
-                unprofiled.append(name)
-            else:
-                step_traffic += tr["bytes_per_launch"] * calls / args.steps
         filter_bytes = bf.num_blocks * 8
         line = {
             "metric": "bloom probe keys/sec (whole node)",
@@ -877,73 +913,92 @@ def main():
                 "probe_strategy": strategy_name,
                 "job_geomean": "not measured: needs DuckDB v1.4.4 + job.duckdb (SURVEY §8f row 1)",
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom_name,
-                "achieved": achieved / 1e9,
-                "peak": HBM_PEAK_BPS / 1e9,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_BPS,
-                "traffic": traffic["bytes_per_launch"] if traffic else None,
-                "traffic_source": traffic["source"] if traffic else None,
-                "avg_launch_ms": dom_ms,
-                "kernel_events": kernel_events,
-                "launches_per_step": dom_calls_per_step,
-                "algorithmic_bytes_per_launch": dom_bytes,
-                # the same kernel against what this box streams (measured in this process, untimed): separates the
-                # box from the code
-                "stream_GBps": stream_cal["read_GBps"] if stream_cal else None,
-                "copy_GBps": stream_cal["copy_GBps"] if stream_cal else None,
-                "frac_of_stream": achieved / 1e9 / stream_cal["read_GBps"] if stream_cal else None,
-                # the kernel's real HBM traffic rate (PMC bytes / its duration) against the box's read + write copy
-                "traffic_frac_of_copy": (traffic["bytes_per_launch"] / (dom_ms * 1e-3) / 1e9 / stream_cal["copy_GBps"]
-                                         if stream_cal and traffic else None),
-            },
-            "stream_calibration": stream_cal if stream_cal else (
-                "skipped: ranks share one GPU (gloo rehearsal)" if shared_device else "skipped (--no-stream-calibration)"),
-            "kernels_ms": {k: v[1] / v[0] for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1][1])},
-            "kernels_launches_per_step": {k: v[0] / args.steps for k, v in ktimes.items()},
-            "probe_total": {
-                "avg_ms": probe_ms,
-                "algorithmic_bytes": probe_bytes,
-                "achieved_GBps": probe_bytes / (probe_ms * 1e-3) / 1e9,
-                "frac": probe_bytes / (probe_ms * 1e-3) / HBM_PEAK_BPS,
-                "frac_of_stream": probe_bytes / (probe_ms * 1e-3) / 1e9 / stream_cal["read_GBps"] if stream_cal else None,
-                # HBM bytes the whole step moves (PMC, every kernel) and their rate over the step
-                "traffic": step_traffic if not unprofiled else None,
-                "traffic_GBps": step_traffic / (probe_ms * 1e-3) / 1e9 if not unprofiled else None,
-                "traffic_frac_of_copy": (step_traffic / (probe_ms * 1e-3) / 1e9 / stream_cal["copy_GBps"]
-                                         if stream_cal and not unprofiled else None),
-                "traffic_unprofiled_kernels": unprofiled,
-            },
-            "build": {
-                "rows": n_build,
-                "insert_ms": insert_s * 1e3,
-                "insert_keys_per_s": (n_build / world) / insert_s if insert_s > 0 else None,
-                # the product merge only (rpt_bf_allreduce_or_ws; workspace allocated before the timer)
-                "or_merge_ms": merge_s * 1e3 if comm is not None else None,
-                "torch_merge_ms": merge_s * 1e3 if world > 1 and comm is None else None,
-                # per-GPU xGMI bytes of the OR all-reduce: 2 (W-1)/W of the filter
-                "or_merge_GBps_per_gpu": (2 * (world - 1) / world * filter_bytes / merge_s / 1e9
-                                          if comm is not None and merge_s > 0 else None),
-                # the merge is direct point-to-point (every rank sends its 1/W slices to every peer, twice):
-                # each of a GPU's W-1 xGMI links carries 2 S / W of it (GB/s per link)
-                "or_merge_GBps_per_link": (2 / world * filter_bytes / merge_s / 1e9
-                                           if comm is not None and merge_s > 0 else None),
-                "merge_check": merge_check,
-                "merge_path": merge_path,
-            },
         }
-        if c5 is not None:
-            line["c5_merge"] = c5
-        if not args.no_cpu_baseline and world == 1:
-            sample = int(args.cpu_sample) if args.cpu_sample else n_probe
-            threads = args.cpu_threads or cpu_share()
-            src = "--cpu-threads" if args.cpu_threads else "this process's CPU share: affinity mask capped by the cgroup quota"
-            cb = cpu_baseline(n_build, n_filter, p_permille, sample, threads, src, args.key_type, args.cpu_lag)
-            if sample == n_probe:  # same rows, same filter: a full-size cross-check of the survivor count
-                cb["survivors_match_gpu"] = cb["survivors"] == survivors
-            line["cpu_baseline"] = cb
+        if args.full:
+            probe_bytes = key_bytes * n_probe + SEL_BYTES * survivors
+            # dominant kernel of the step (largest total device time)
+            dom_name, (dom_calls, dom_total) = max(ktimes.items(), key=lambda kv: kv[1][1])
+            dom_ms = dom_total / dom_calls
+            dom_calls_per_step = dom_calls / args.steps
+            dom_bytes = algorithmic_bytes(dom_name, n_probe, survivors, key_bytes) / dom_calls_per_step
+            achieved = dom_bytes / (dom_ms * 1e-3)
+            traffic = pmc_traffic(dom_name, tag)
+            # whole-step HBM traffic: every kernel of the step at its PMC bytes per launch
+            step_traffic, unprofiled = 0.0, []
+            for name, (calls, _total) in ktimes.items():
+                tr = pmc_traffic(name, tag)
+                if tr is None:
+                    unprofiled.append(name)
+                else:
+                    step_traffic += tr["bytes_per_launch"] * calls / args.steps
+            line.update({
+                "roofline": {
+                    "bound": "hbm",
+                    "kernel": dom_name,
+                    "achieved": achieved / 1e9,
+                    "peak": HBM_PEAK_BPS / 1e9,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_BPS,
+                    "traffic": traffic["bytes_per_launch"] if traffic else None,
+                    "traffic_source": traffic["source"] if traffic else None,
+                    "avg_launch_ms": dom_ms,
+                    "kernel_events": kernel_events,
+                    "launches_per_step": dom_calls_per_step,
+                    "algorithmic_bytes_per_launch": dom_bytes,
+                    # the same kernel against what this box streams (measured in this process, untimed): separates the
+                    # box from the code
+                    "stream_GBps": stream_cal["read_GBps"] if stream_cal else None,
+                    "copy_GBps": stream_cal["copy_GBps"] if stream_cal else None,
+                    "frac_of_stream": achieved / 1e9 / stream_cal["read_GBps"] if stream_cal else None,
+                    # the kernel's real HBM traffic rate (PMC bytes / its duration) against the box's read + write copy
+                    "traffic_frac_of_copy": (traffic["bytes_per_launch"] / (dom_ms * 1e-3) / 1e9 / stream_cal["copy_GBps"]
+                                             if stream_cal and traffic else None),
+                },
+                "stream_calibration": stream_cal if stream_cal else (
+                    "skipped: ranks share one GPU (gloo rehearsal)" if shared_device else "skipped (--no-stream-calibration)"),
+                "kernels_ms": {k: v[1] / v[0] for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1][1])},
+                "kernels_launches_per_step": {k: v[0] / args.steps for k, v in ktimes.items()},
+                "probe_total": {
+                    "avg_ms": probe_ms,
+                    "algorithmic_bytes": probe_bytes,
+                    "achieved_GBps": probe_bytes / (probe_ms * 1e-3) / 1e9,
+                    "frac": probe_bytes / (probe_ms * 1e-3) / HBM_PEAK_BPS,
+                    "frac_of_stream": probe_bytes / (probe_ms * 1e-3) / 1e9 / stream_cal["read_GBps"] if stream_cal else None,
+                    # HBM bytes the whole step moves (PMC, every kernel) and their rate over the step
+                    "traffic": step_traffic if not unprofiled else None,
+                    "traffic_GBps": step_traffic / (probe_ms * 1e-3) / 1e9 if not unprofiled else None,
+                    "traffic_frac_of_copy": (step_traffic / (probe_ms * 1e-3) / 1e9 / stream_cal["copy_GBps"]
+                                             if stream_cal and not unprofiled else None),
+                    "traffic_unprofiled_kernels": unprofiled,
+                },
+                "build": {
+                    "rows": n_build,
+                    "insert_ms": insert_s * 1e3,
+                    "insert_keys_per_s": (n_build / world) / insert_s if insert_s > 0 else None,
+                    # the product merge only (rpt_bf_allreduce_or_ws; workspace allocated before the timer)
+                    "or_merge_ms": merge_s * 1e3 if comm is not None else None,
+                    "torch_merge_ms": merge_s * 1e3 if world > 1 and comm is None else None,
+                    # per-GPU xGMI bytes of the OR all-reduce: 2 (W-1)/W of the filter
+                    "or_merge_GBps_per_gpu": (2 * (world - 1) / world * filter_bytes / merge_s / 1e9
+                                              if comm is not None and merge_s > 0 else None),
+                    # the merge is direct point-to-point (every rank sends its 1/W slices to every peer, twice):
+                    # each of a GPU's W-1 xGMI links carries 2 S / W of it (GB/s per link)
+                    "or_merge_GBps_per_link": (2 / world * filter_bytes / merge_s / 1e9
+                                               if comm is not None and merge_s > 0 else None),
+                    "merge_check": merge_check,
+                    "merge_path": merge_path,
+                },
+            })
+            if c5 is not None:
+                line["c5_merge"] = c5
+            if not args.no_cpu_baseline and world == 1:
+                sample = int(args.cpu_sample) if args.cpu_sample else n_probe
+                threads = args.cpu_threads or cpu_share()
+                src = "--cpu-threads" if args.cpu_threads else "this process's CPU share: affinity mask capped by the cgroup quota"
+                cb = cpu_baseline(n_build, n_filter, p_permille, sample, threads, src, args.key_type, args.cpu_lag)
+                if sample == n_probe:  # same rows, same filter: a full-size cross-check of the survivor count
+                    cb["survivors_match_gpu"] = cb["survivors"] == survivors
+                line["cpu_baseline"] = cb
         print(json.dumps(line), file=record_out, flush=True)
 
     if comm is not None:

@@ -107,6 +107,42 @@ def test_c5_merge_flags(monkeypatch):
     assert a.c5_merge and a.c5_rows_per_rank == 1e7 and a.collective_timeout_ms == 5000
 
 
+def test_full_and_dump_flags(monkeypatch):
+    # a plain run does the headline only; everything beside it is behind --full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "somewhere"
+    # measurements that only exist beside the headline refuse to be dropped quietly
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--c5-merge"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 .npy files: the whole selection vector when small, else the entries at seeded
+    positions (equal from call to call), and a summary over every entry (count, sum as two 32-bit halves)."""
+    import numpy as np
+    import torch
+
+    sel = np.arange(0, 3000, 3, dtype=np.int64)
+    sel[-1] = 0xFFFFFFF0  # a uint32 entry above 2^31 lives in the int32 tensor as a negative value
+    out_sel = torch.from_numpy(np.concatenate([sel, np.full(24, 77)]).astype(np.uint32).view(np.int32))
+    bench.dump_outputs(str(tmp_path / "a"), out_sel, sel.size)
+    got = np.load(tmp_path / "a" / "sel.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, sel.astype(np.float64))
+    total = int(sel.sum())
+    assert np.load(tmp_path / "a" / "sel_summary.npy").tolist() == [sel.size, total & 0xFFFFFFFF, total >> 32]
+    monkeypatch.setattr(bench, "DUMP_SEL_SAMPLE", 100)
+    bench.dump_outputs(str(tmp_path / "b"), out_sel, sel.size, "_rank1")
+    bench.dump_outputs(str(tmp_path / "c"), out_sel, sel.size, "_rank1")
+    b, c = np.load(tmp_path / "b" / "sel_rank1.npy"), np.load(tmp_path / "c" / "sel_rank1.npy")
+    assert b.shape == (100,) and np.array_equal(b, c) and np.all(np.diff(b) >= 0) and np.isin(b, sel).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "sel_summary_rank1.npy"), np.load(tmp_path / "a" / "sel_summary.npy"))
+
+
 def test_kernel_events_flag(monkeypatch):
     # per-kernel timing events run in a second pass by default (they cost ~25 us per step inside the timed steps)
     monkeypatch.setattr(sys, "argv", ["bench.py"])

@@ -1,6 +1,6 @@
 """The driver's multi-GPU bench run, rehearsed end to end on ONE GPU.
 
-`bench.py --gpus N` at N > 1 runs the headline (sharded C2 build, OR merge, merge check, sharded probe) and
+`bench.py --full --gpus N` at N > 1 runs the headline (sharded C2 build, OR merge, merge check, sharded probe) and
 then the `c5_merge` section: every rank inserts its shard of the N x rows build column into the 8 GiB filter
 sized for 8e9 rows, the partials are OR-merged, the merged filter is checked against a single build of all
 rows on every rank, and every rank probes its slice (the cross-GPU counterpart of PhysicalCreateBF::Combine,
@@ -34,7 +34,7 @@ def run_bench(world: int, tmp_path):
     out_dir = os.path.join(REPO, "gpurun_out")
     os.makedirs(out_dir, exist_ok=True)
     log = os.path.join(out_dir, f"bench_rehearsal_n{world}.log")
-    cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--full", "--gpus", str(world), "--steps", "2", "--warmup", "1",
            "--probe-rows", "2e7", "--no-cpu-baseline", "--c5-rows-per-rank", str(ROWS), "--c5-merge-reps", "1"]
     env = dict(os.environ, RPT_BENCH_BACKEND="gloo")
     with open(log, "w") as f:

@@ -158,7 +158,7 @@ def test_two_rank_allreduce_matches_single_build(n_build, empty_rank):
 
 def test_bench_c5_merge_section_one_rank():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1", "--probe-rows", "1e7",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--probe-rows", "1e7",
            "--no-cpu-baseline", "--c5-merge", "--c5-rows-per-rank", "2e7", "--collective-timeout-ms", "60000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
