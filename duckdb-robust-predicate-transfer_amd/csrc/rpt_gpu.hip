@@ -459,7 +459,18 @@ uint32_t bucket_count(int log_num_blocks) {
 #ifndef RPT_SLICE_SKEW_MULT
 #define RPT_SLICE_SKEW_MULT 32
 #endif
-std::atomic<uint32_t> g_skew_epoch{0};
+// Stamps of the eager skewed partitioned probes: 2, 3, ... (0 is what a captured probe's memset leaves, 1 the
+// stamp every captured probe uses, so an eager call's stamp is never a captured one's, wrap-around included).
+std::atomic<uint32_t> g_skew_epoch{1};
+uint32_t skew_epoch_after(uint32_t last) { return last + 1 < 2 ? 2u : last + 1; }
+uint32_t next_skew_epoch() {
+  uint32_t last = g_skew_epoch.load();
+  while (!g_skew_epoch.compare_exchange_weak(last, skew_epoch_after(last))) {
+  }
+  return skew_epoch_after(last);
+}
+// Workspaces are read and written in 16-B pieces at 256-B part offsets (rpt_gpu.h: 16-B aligned base).
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 int strategy_supported(int strategy, int log_num_blocks) {
   constexpr int kBucketLog = rpt::kSliceLog + rpt::kBucketSliceLog;  // log2 blocks per bucket (22)
   switch (strategy) {
@@ -1323,6 +1334,7 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
   const size_t need = insert_workspace_layout(n, L, strategy, nullptr, nullptr);
   if (!workspace || workspace_bytes < need)
     return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
   RPT_ON_DEVICE(bf->device);
   hipStream_t s = as_stream(stream);
   RPT_REFUSE_CAPTURE_WRITE(bf, s, "insert");
@@ -1440,6 +1452,7 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
   const size_t need = workspace_layout(n, L, strategy, nullptr, nullptr);
   if (!workspace || workspace_bytes < need)
     return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
   RPT_ON_DEVICE(bf->device);
   ProbeWorkspace ws;
   workspace_layout(n, L, strategy, workspace, &ws);
@@ -1517,7 +1530,7 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
         skew.epoch = 1;
         RPT_HIP(hipMemsetAsync(ws.heavy, 0, sizeof(uint32_t) * tile_slices, s));
       } else {
-        skew.epoch = g_skew_epoch.fetch_add(1) + 1;  // a fresh stamp per call: nothing to clear
+        skew.epoch = next_skew_epoch();  // a fresh stamp (>= 2) per call: nothing to clear
       }
     }
     int st2 = transpose_u32(s, ws.runs_tm, n_tiles, tile_slices, ws.runs, skewed ? ws.heavy : nullptr,
@@ -1623,6 +1636,7 @@ int rpt_bf_probe_phase2(const rpt_bf* bf, const uint32_t* row_sel, uint64_t n, u
   const size_t need = workspace_layout(n, L, strategy, nullptr, nullptr);
   if (!workspace || workspace_bytes < need)
     return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
   ProbeWorkspace ws;
   workspace_layout(n, L, strategy, workspace, &ws);
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
@@ -1760,6 +1774,12 @@ int rpt_keys_widen(const uint32_t* lo, const uint32_t* chunk_hi, const uint32_t*
 int rpt_words_or_slices(uint64_t* dst, const uint64_t* srcs, uint32_t k, uint64_t n_words, rpt_stream_t stream) {
   if (!dst || (!srcs && k > 0)) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
   if (n_words == 0) return RPT_OK;
+  // or_slices_kernel reads dst and every slice in 16-B pieces: slice s starts at srcs + s * n_words words
+  if (misaligned16(dst) || (k > 0 && misaligned16(srcs)))
+    return fail(RPT_ERR_INVALID_ARGUMENT, "dst and srcs must be 16-byte aligned");
+  if (k >= 2 && (n_words & 1))
+    return fail(RPT_ERR_INVALID_ARGUMENT, "n_words=%llu is odd: with k >= 2 every second slice would not be 16-byte aligned",
+                static_cast<unsigned long long>(n_words));
   const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n_words / 2, rpt::kBlockThreads), 8192)));
   ProfScope prof12_("or_slices_kernel", as_stream(stream));
   hipLaunchKernelGGL(rpt::or_slices_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, as_stream(stream), dst, srcs, k,
@@ -1772,6 +1792,7 @@ int rpt_words_or_slices(uint64_t* dst, const uint64_t* srcs, uint32_t k, uint64_
 int rpt_words_or(uint64_t* dst, const uint64_t* src, uint64_t n_words, rpt_stream_t stream) {
   if (!dst || !src) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
   if (n_words == 0) return RPT_OK;
+  if (misaligned16(dst) || misaligned16(src)) return fail(RPT_ERR_INVALID_ARGUMENT, "dst and src must be 16-byte aligned");
   const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n_words / 2, rpt::kBlockThreads), 8192)));
   ProfScope prof13_("or_slices_kernel", as_stream(stream));
   hipLaunchKernelGGL(rpt::or_slices_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, as_stream(stream), dst, src, 1u,
@@ -2366,6 +2387,7 @@ int rpt_testing_set_rccl_api(const rpt_rccl_api_table* table) {
 }
 uint64_t rpt_testing_bucketed_insert_batch(void) { return kBucketedInsertBatch; }
 void rpt_testing_force_l1_error(int on) { g_force_l1_error.store(on != 0); }
+uint32_t rpt_testing_next_skew_epoch(void) { return skew_epoch_after(g_skew_epoch.load()); }
 #endif  // RPT_TESTING_HOOKS
 
 int rpt_bf_count_bits(const rpt_bf* bf, uint64_t* out) {

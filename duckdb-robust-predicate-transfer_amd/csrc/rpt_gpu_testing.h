@@ -57,6 +57,10 @@ uint64_t rpt_testing_bucketed_insert_batch(void);
 /* Test build only: on != 0 makes every later bucketed level 1 hit its chunk bound (the never-expected
  * error path: the probe must then pass every row and the insert set every filter bit). */
 void rpt_testing_force_l1_error(int on);
+/* Test build only: the stamp the next eager (not captured) skewed partitioned probe writes into its
+ * workspace's per-slice skew words for the slices its keys overload (>= 2; a captured probe uses 1). A test
+ * pre-fills a workspace with it to make every slice look overloaded: the result must not change. */
+uint32_t rpt_testing_next_skew_epoch(void);
 #endif
 
 #ifdef __cplusplus

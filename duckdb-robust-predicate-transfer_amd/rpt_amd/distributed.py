@@ -50,8 +50,11 @@ def gpu_or_slices(dst: torch.Tensor, srcs: torch.Tensor, k: int, n_words: int) -
 
 
 def padded_words(num_words: int, world: int) -> int:
-    """Smallest multiple of `world` >= num_words (filters are 2^k words; world may be any size)."""
-    return ((num_words + world - 1) // world) * world
+    """Smallest multiple of 2 * `world` >= num_words (filters are 2^k words; world may be any size). Every
+    rank's slice is then an even number of words: rpt_words_or_slices reads its slices in 16-B pieces and
+    rejects an odd slice length."""
+    step = 2 * world
+    return ((num_words + step - 1) // step) * step
 
 
 def or_allreduce_words(full: torch.Tensor, group=None, or_slices: Optional[OrSlices] = None) -> None:

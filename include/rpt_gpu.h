@@ -20,6 +20,17 @@
  *   CONSTANT    flatten on the host first (PTBloomFilter's HashColumns flattens, bloom_filter.cpp:19-21)
  * Validity is DuckDB's ValidityMask layout: uint64 words, bit (i % 64) of word (i / 64) set = valid;
  * NULL pointer = all rows valid.
+ *
+ * Caller buffers (workspaces and outputs):
+ *   - Contents on entry are ARBITRARY. A workspace may hold anything: the leftovers of another call, filter,
+ *     strategy or batch size, or a fill pattern; an output buffer likewise. No entry point needs them cleared,
+ *     and no result depends on what they held. (What a call leaves in its workspace is unspecified.)
+ *   - Nothing outside the documented sizes is written: a workspace of exactly rpt_*_workspace_bytes() bytes,
+ *     out_sel of exactly n entries, out_bits of exactly ceil(n/512)*8 words, out_count of one uint64, and an
+ *     out_hashes / out array of exactly n entries are enough, with no slack behind them.
+ *   - A workspace base must be 16-byte aligned (hipMalloc gives 256): other bases are rejected with
+ *     RPT_ERR_INVALID_ARGUMENT before anything is launched. Output arrays should be 16-byte aligned as well
+ *     (not checked, except by rpt_words_or and rpt_words_or_slices); out_count needs 8.
  */
 #ifndef RPT_GPU_H
 #define RPT_GPU_H
@@ -187,7 +198,8 @@ int rpt_bf_insert(rpt_bf* bf, const rpt_key_column* col, uint64_t n, rpt_stream_
  * batches (same result, same thread-safety). workspace: rpt_insert_workspace_bytes(n,
  * log_num_blocks) bytes of device memory (the largest any insert strategy needs; 0 when the filter
  * only supports atomic inserts), or rpt_bf_insert_workspace_bytes(bf, n) for the strategy this
- * insert will run (0 = atomic, no workspace needed). */
+ * insert will run (0 = atomic, no workspace needed). The workspace is 16-byte aligned and may hold anything on
+ * entry (see "Caller buffers" above). */
 size_t rpt_insert_workspace_bytes(uint64_t n_rows, int log_num_blocks);
 size_t rpt_bf_insert_workspace_bytes(const rpt_bf* bf, uint64_t n_rows);
 int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* workspace, size_t workspace_bytes,
@@ -210,7 +222,8 @@ int rpt_bf_set_minmax(rpt_bf* bf, int64_t min_value, int64_t max_value, int has_
  * *out_count_dev (device uint64). Rows are 0..n-1, or row_sel[0..n) when row_sel != NULL (the
  * already-sliced chunk of PhysicalUseBF's multi-filter loop, physical_use_bf.cpp:137-183); the
  * written ids are then the row_sel values. n must be < 2^32 (sel_t is uint32). out_sel capacity n.
- * workspace: device memory of rpt_probe_workspace_bytes(n, log_num_blocks) bytes, exclusively owned by this call
+ * workspace: device memory of rpt_probe_workspace_bytes(n, log_num_blocks) bytes (or rpt_bf_probe_workspace_bytes),
+ * 16-byte aligned, holding anything on entry (see "Caller buffers" above), exclusively owned by this call
  * until it completes on `stream`. Batches of at most RPT_SMALL_PROBE_ROWS rows under the AUTO strategy
  * run one fused single-workgroup kernel (probe + compaction: one launch instead of four) and leave
  * the workspace untouched. */
@@ -347,10 +360,13 @@ int rpt_rccl_comm_init_rank_nonblocking(int device, int world, const uint8_t* id
  * timeout; aborted if it does not complete), so its teardown has finished when this returns. */
 int rpt_rccl_comm_destroy(void* comm);
 /* dst[i] |= src[i] for n_words words (device pointers): the local step of the multi-GPU
- * OR all-reduce (reduce-scatter slices). */
+ * OR all-reduce (reduce-scatter slices). dst and src must be 16-byte aligned (RPT_ERR_INVALID_ARGUMENT
+ * otherwise); n_words may be odd. */
 int rpt_words_or(uint64_t* dst, const uint64_t* src, uint64_t n_words, rpt_stream_t stream);
 /* dst[i] = src_0[i] | src_1[i] | ... | src_{k-1}[i], srcs given as k contiguous slices of
- * n_words words starting at `srcs` (a receive buffer of k peer slices). */
+ * n_words words starting at `srcs` (a receive buffer of k peer slices). dst and every slice are read and
+ * written in 16-byte pieces: dst and srcs must be 16-byte aligned, and with k >= 2 n_words must be even (slice
+ * s starts at srcs + s * n_words). Anything else is rejected with RPT_ERR_INVALID_ARGUMENT before any launch. */
 int rpt_words_or_slices(uint64_t* dst, const uint64_t* srcs, uint32_t k, uint64_t n_words, rpt_stream_t stream);
 /* BlockedBloomFilter::IsSameAs (pyarrow 25 arrow/acero/bloom_filter.h:131): *out_same = 1 iff both filters
  * have the same log_num_blocks and every word is equal, compared on the device (no host copy of either

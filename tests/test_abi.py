@@ -136,6 +136,31 @@ def test_testing_hook_absent_from_product():
     lib = _lib.load()
     assert not hasattr(lib, "rpt_testing_set_rccl_api")
     assert not hasattr(lib, "rpt_testing_bucketed_insert_batch")
+    assert not hasattr(lib, "rpt_testing_force_l1_error")
+    assert not hasattr(lib, "rpt_testing_next_skew_epoch")
+    # ... and does in the test build
+    tlib = ctypes.CDLL(os.path.join(REPO, "tests", "loopback", "build", "librpt_gpu_testing.so"))
+    assert hasattr(tlib, "rpt_testing_next_skew_epoch")
+
+
+def test_words_or_rejects_what_its_16_byte_accesses_cannot_take():
+    """rpt_words_or_slices reads dst and every slice in 16-B pieces; slice s starts at srcs + s * n_words words, so
+    with an odd n_words every second slice would be misaligned. The checks return before any launch: the
+    pointers here are made-up values, never dereferenced."""
+    lib = _lib.load()
+    dst, srcs = 0x7F0000001000, 0x7F0000100000  # 16-B aligned, not real allocations
+    for n_words, k in [(1, 2), (3, 2), (513, 3), (100_003, 8)]:
+        assert lib.rpt_words_or_slices(dst, srcs, k, n_words, None) == _lib.RPT_ERR_INVALID_ARGUMENT, (n_words, k)
+        assert b"odd" in lib.rpt_last_error()
+    for off in (8, 4, 1):
+        assert lib.rpt_words_or_slices(dst + off, srcs, 2, 4, None) == _lib.RPT_ERR_INVALID_ARGUMENT
+        assert b"aligned" in lib.rpt_last_error()
+        assert lib.rpt_words_or_slices(dst, srcs + off, 2, 4, None) == _lib.RPT_ERR_INVALID_ARGUMENT
+        assert lib.rpt_words_or_slices(dst, srcs + off, 1, 3, None) == _lib.RPT_ERR_INVALID_ARGUMENT
+        assert lib.rpt_words_or(dst + off, srcs, 4, None) == _lib.RPT_ERR_INVALID_ARGUMENT
+        assert lib.rpt_words_or(dst, srcs + off, 4, None) == _lib.RPT_ERR_INVALID_ARGUMENT
+    # nothing to do is still nothing to do
+    assert lib.rpt_words_or_slices(dst + 8, srcs, 2, 0, None) == _lib.RPT_OK
 
 
 @pytest.mark.parametrize("world,L", [(1, 30), (2, 3), (2, 20), (3, 25), (8, 24), (8, 30), (8, 31)])

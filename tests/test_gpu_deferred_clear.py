@@ -3,12 +3,12 @@ partitioned / bucketed insert whose slice merge owns every slice stores the slic
 included), every other operation zeroes the words first. Each case fills the filter with keys A, clears
 it, then runs one operation: the result must equal the oracle's for an EMPTY filter followed by that
 operation (no bit of A survives), and the filter must keep composing with later inserts. Bit-exact."""
-import gc
 import numpy as np
 import pytest
 import torch
 
 import rpt_oracle as orc
+from buf_util import graph_destroy, graph_instantiate, graph_launch, hip_graph_api, stream_capture
 
 pytestmark = pytest.mark.gpu
 
@@ -214,10 +214,7 @@ def test_graph_capture_of_a_cleared_filter(rpt, log_nb, n, mode):
 
     from rpt_amd._lib import RptError
 
-    hip = ctypes.CDLL("libamdhip64.so")
-    for fn in ("hipStreamBeginCapture", "hipStreamEndCapture", "hipGraphInstantiate", "hipGraphLaunch",
-               "hipGraphExecDestroy", "hipGraphDestroy"):
-        getattr(hip, fn).restype = ctypes.c_int
+    hip = hip_graph_api()
     bf = filled(rpt, log_nb)
     bf.clear()
     p = keys(n, 7)
@@ -233,21 +230,15 @@ def test_graph_capture_of_a_cleared_filter(rpt, log_nb, n, mode):
     sh = ctypes.c_void_p(s.cuda_stream)
     graph, exe = ctypes.c_void_p(), ctypes.c_void_p()
 
-    def capture():
-        # as torch.cuda.graph prepares a capture: collect garbage first (a filter an earlier test left to the cycle
-        # collector is freed by rpt_bf_destroy -> hipFree, which would invalidate a global-mode capture from any
-        # thread of the process) and keep the collector off inside the capture window
-        gc.collect()
-        torch.cuda.synchronize()
-        gc.disable()
-        assert hip.hipStreamBeginCapture(sh, mode) == 0
-        err = None
+    def probe():
         try:
             bf.probe_async(kp, n=n, out_sel=out_sel, out_count=out_count, workspace=ws, stream=s)
         except RptError as e:
-            err = e
-        st = hip.hipStreamEndCapture(sh, ctypes.byref(graph))
-        gc.enable()
+            return e
+        return None
+
+    def capture():
+        st, err = stream_capture(sh, mode, graph, probe)  # (garbage collected first: see buf_util.stream_capture)
         assert st == 0  # still a valid capture
         return err
 
@@ -257,7 +248,7 @@ def test_graph_capture_of_a_cleared_filter(rpt, log_nb, n, mode):
     bf.settle()
     bf.insert(dev(b))
     assert capture() is None
-    assert hip.hipGraphInstantiate(ctypes.byref(exe), graph, None, None, ctypes.c_size_t(0)) == 0
+    assert graph_instantiate(graph, exe) == 0
     ref = orc.new_words(log_nb)
     orc.insert_keys(ref, log_nb, b)
     for extra in (None, c):
@@ -265,13 +256,13 @@ def test_graph_capture_of_a_cleared_filter(rpt, log_nb, n, mode):
             bf.insert(dev(extra))
             orc.insert_keys(ref, log_nb, extra)
         torch.cuda.synchronize()
-        assert hip.hipGraphLaunch(exe, sh) == 0
+        assert graph_launch(exe, sh) == 0
         s.synchronize()
         cnt = int(out_count.item())
         want = orc.probe_keys(ref, log_nb, p)
         assert np.array_equal(out_sel[:cnt].cpu().numpy().view(np.uint32), want)
     assert np.array_equal(bf.export_words(), ref)
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    assert graph_destroy(exe, graph)
 
 
 @pytest.mark.parametrize("mode", [2, 0])  # relaxed; global, where the library's event query must not break the capture
@@ -288,10 +279,7 @@ def test_graph_capture_of_inserts(rpt, strategy, log_nb, mode):
 
     from rpt_amd._lib import check
 
-    hip = ctypes.CDLL("libamdhip64.so")
-    for fn in ("hipStreamBeginCapture", "hipStreamEndCapture", "hipGraphInstantiate", "hipGraphLaunch",
-               "hipGraphExecDestroy", "hipGraphDestroy"):
-        getattr(hip, fn).restype = ctypes.c_int
+    hip = hip_graph_api()
     bf = filled(rpt, log_nb)
     lib = bf._lib
     n = 3_000_000 if strategy != INS_ATOMIC else 200_000
@@ -306,13 +294,7 @@ def test_graph_capture_of_inserts(rpt, strategy, log_nb, mode):
     graph, exe = ctypes.c_void_p(), ctypes.c_void_p()
 
     def capture(op):
-        gc.collect()  # see test_graph_capture_of_a_cleared_filter
-        torch.cuda.synchronize()
-        gc.disable()
-        assert hip.hipStreamBeginCapture(sh, mode) == 0
-        st = op()
-        end = hip.hipStreamEndCapture(sh, ctypes.byref(graph))
-        gc.enable()
+        end, st = stream_capture(sh, mode, graph, op)
         assert end == 0  # still a valid capture
         return st
 
@@ -328,7 +310,7 @@ def test_graph_capture_of_inserts(rpt, strategy, log_nb, mode):
     bf.settle()
     bf.insert(dev(c))
     assert capture(insert_b) == 0, lib.rpt_last_error().decode()
-    assert hip.hipGraphInstantiate(ctypes.byref(exe), graph, None, None, ctypes.c_size_t(0)) == 0
+    assert graph_instantiate(graph, exe) == 0
     ref = orc.new_words(log_nb)
     orc.insert_keys(ref, log_nb, c)  # the clear dropped the filled keys; the capture inserted nothing yet
     torch.cuda.synchronize()
@@ -339,9 +321,9 @@ def test_graph_capture_of_inserts(rpt, strategy, log_nb, mode):
             bf.insert(dev(extra))
             orc.insert_keys(ref, log_nb, extra)
         torch.cuda.synchronize()
-        assert hip.hipGraphLaunch(exe, sh) == 0
+        assert graph_launch(exe, sh) == 0
         s.synchronize()
         assert np.array_equal(bf.export_words(), ref)
     probe = np.concatenate([b[:20_000], keys(20_000, 14), d[:1000]])
     assert np.array_equal(bf.lookup_sel(dev(probe)).cpu().numpy().astype(np.uint32), orc.probe_keys(ref, log_nb, probe))
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    assert graph_destroy(exe, graph)

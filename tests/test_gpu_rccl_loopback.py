@@ -39,6 +39,7 @@ import pytest
 import torch
 
 import rpt_oracle as orc
+from buf_util import FF, GuardedBuffer
 from conftest import REPO
 
 pytestmark = pytest.mark.gpu
@@ -160,18 +161,24 @@ def build_partials(tlib, world, log_nb, n_build, empty):
 
 
 def allreduce_all(tlib, bfs, comms):
+    """Every rank's staging is exactly rpt_allreduce_workspace_bytes bytes between guard bands and starts out
+    as 0xFF bytes: garbage in the staging must never be ORed into a filter (world need not divide the block
+    count, so the ranks' pieces differ in length), and nothing may be written outside it."""
     world = len(bfs)
     L = bfs[0].log_num_blocks
     need = tlib.rpt_allreduce_workspace_bytes(world, L)
-    wss = [torch.empty(need, dtype=torch.uint8, device="cuda:0") for _ in range(world)]
+    wss = [GuardedBuffer(need).poison(FF) for _ in range(world)]
     streams = [torch.cuda.Stream(device="cuda:0") for _ in range(world)]
     st = [None] * world
+    torch.cuda.synchronize()  # the fills ran on the default stream
 
     def run(r):
-        st[r] = tlib.rpt_bf_allreduce_or_ws(bfs[r].handle, comms[r], wss[r].data_ptr(), need, streams[r].cuda_stream)
+        st[r] = tlib.rpt_bf_allreduce_or_ws(bfs[r].handle, comms[r], wss[r].ptr, need, streams[r].cuda_stream)
 
     in_threads(world, run)
     torch.cuda.synchronize()
+    for r, ws in enumerate(wss):
+        ws.assert_guards_intact(f"rank {r} staging")
     return st, need
 
 
