@@ -11,6 +11,8 @@
 //               LDS          probe_direct.hpp  filters <= 64 KiB staged whole in LDS
 //               PARTITIONED  partitioned.hpp   rows routed by 128 KiB filter slice; slices in LDS
 //               BUCKETED     bucketed.hpp      two levels for filters of 32 MiB..16 GiB
+//             chain of filters (rpt_bf_probe_chain_ws): stage 0 as above, every later stage ANDs its filter
+//             into the result bits in place (probe_chain.hpp), one phase 2 at the end.
 //             phase 2 = two-level scan + expansion into an ascending uint32 sel (compaction.hpp).
 //   insert  : atomic OR per key (misc.hpp), or the partitioned / bucketed routing with the slices
 //             ORed in LDS; the build's key min/max is folded in on the way.
@@ -41,6 +43,7 @@
 
 #include "kernels/common.hpp"
 #include "kernels/probe_direct.hpp"
+#include "kernels/probe_chain.hpp"
 #include "kernels/partitioned.hpp"
 #include "kernels/bucketed.hpp"
 #include "kernels/compaction.hpp"
@@ -752,6 +755,14 @@ unsigned persistent_grid(int device, uint64_t n_segs) {
   return static_cast<unsigned>(std::max<uint64_t>(1, std::min(want, cap)));
 }
 
+// Grid of the LDS probes (whole filter or hybrid): 1024-thread workgroups, as many per CU as their LDS allows.
+unsigned lds_probe_grid(int device, int log_num_blocks, uint64_t n_segs) {
+  const uint64_t lds = (8ULL << std::min(log_num_blocks, rpt::kLdsDirectMaxLog)) + 8ULL * rpt::kNumMasks;
+  const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(rpt::kBlocksPerCU, (160ULL << 10) / lds));
+  const uint64_t waves = rpt::kLdsProbeThreads / 64;  // launch_probe_bits_lds_t
+  return static_cast<unsigned>(std::max<uint64_t>(1, std::min(ceil_div(n_segs, waves), num_cus(device) * per_cu)));
+}
+
 template <int K, bool D>
 void launch_probe_bits_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
                          uint64_t n_segs, uint64_t* bits, uint32_t* counts, uint64_t* zero = nullptr,
@@ -807,6 +818,42 @@ void allow_dynamic_lds(const void* fn) {
   if (hipFuncGetAttributes(&at, fn) == hipSuccess) stat = at.sharedSizeBytes;
   (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>((160u << 10) - stat));
   (void)hipGetLastError();
+}
+
+// The masked twins (probe_chain.hpp) of the three direct probes, with their grids and LDS: a chain's stage i >= 1.
+template <int K, bool D>
+void launch_probe_bits_masked_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
+                                uint64_t n_segs, uint64_t* acc, uint32_t* counts) {
+  ProfScope prof(inst_name<K, D, false, rpt::kBlockThreads>("probe_bits_masked_kernel"), s);
+  hipLaunchKernelGGL((rpt::probe_bits_masked_kernel<K, D, false>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
+                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc, counts);
+  prof.end();
+}
+template <int K, bool D>
+void launch_probe_bits_masked_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
+                                    uint64_t n_segs, uint64_t* acc, uint32_t* counts) {
+  if (bf->log_num_blocks > rpt::kLdsDirectMaxLog) {  // hybrid: the first 128 KiB in LDS, the rest from L2
+    const size_t lds = 8ULL << rpt::kLdsDirectMaxLog;
+    static std::once_flag once_h;
+    std::call_once(once_h, [] {
+      allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_masked_hybrid_kernel<K, D>));
+    });
+    ProfScope prof(inst_name<K, D>("probe_bits_masked_hybrid_kernel"), s);
+    hipLaunchKernelGGL((rpt::probe_bits_masked_hybrid_kernel<K, D>), dim3(grid), dim3(rpt::kLdsProbeThreads), lds, s,
+                       bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc, counts);
+    prof.end();
+    return;
+  }
+  const size_t lds = 8ULL << bf->log_num_blocks;
+  static std::once_flag once;  // > 64 KiB of dynamic LDS must be opted into
+  std::call_once(once, [] {
+    allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_masked_kernel<K, D, true, rpt::kLdsProbeThreads>));
+  });
+  ProfScope prof(inst_name<K, D, true, rpt::kLdsProbeThreads>("probe_bits_masked_kernel"), s);
+  hipLaunchKernelGGL((rpt::probe_bits_masked_kernel<K, D, true, rpt::kLdsProbeThreads>), dim3(grid),
+                     dim3(rpt::kLdsProbeThreads), lds, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc,
+                     counts);
+  prof.end();
 }
 
 template <int K, bool D, bool MM, int TM, int SP = 0>
@@ -1437,9 +1484,11 @@ int rpt_bf_find_bits(const rpt_bf* bf, const rpt_key_column* col, uint64_t n, ui
 
 // Phase 1 of rpt_bf_probe. With out_sel (rpt_bf_probe only) the plain PARTITIONED pipeline ends in the
 // fused selection-vector tail instead of the result bits, and *done is set: phase 2 is skipped.
+// counts_out (rpt_bf_probe_chain_ws): the per-segment counts go there instead of into the workspace.
 static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
                              void* workspace, size_t workspace_bytes, rpt_stream_t stream, uint32_t* out_sel,
-                             uint64_t* out_count_dev, bool* done, uint64_t* bits_out = nullptr) {
+                             uint64_t* out_count_dev, bool* done, uint64_t* bits_out = nullptr,
+                             uint32_t* counts_out = nullptr) {
   if (!bf) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter");
   if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
   if (n == 0) return RPT_OK;
@@ -1457,6 +1506,7 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
   ProbeWorkspace ws;
   workspace_layout(n, L, strategy, workspace, &ws);
   if (bits_out) ws.bits = bits_out;  // rpt_bf_probe_bits: the result bits go to the caller's buffer
+  if (counts_out) ws.seg_counts = counts_out;
   hipStream_t s = as_stream(stream);
   RPT_SETTLE(bf, s);
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
@@ -1474,11 +1524,7 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
                     ws.lb_state, lb_words);
     RPT_LAUNCHED("probe_bits_kernel");
   } else if (strategy == RPT_PROBE_LDS) {
-    const uint64_t lds = (8ULL << std::min(L, rpt::kLdsDirectMaxLog)) + 8ULL * rpt::kNumMasks;
-    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(rpt::kBlocksPerCU, (160ULL << 10) / lds));
-    const uint64_t waves = rpt::kLdsProbeThreads / 64;  // launch_probe_bits_lds_t
-    const unsigned grid = static_cast<unsigned>(
-        std::max<uint64_t>(1, std::min(ceil_div(n_segs, waves), num_cus(bf->device) * per_cu)));
+    const unsigned grid = lds_probe_grid(bf->device, L, n_segs);
     RPT_DISPATCH_KD(launch_probe_bits_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts,
                     ws.lb_state, lb_words);
     RPT_LAUNCHED("probe_bits_kernel<lds>");
@@ -1620,6 +1666,30 @@ int rpt_bf_probe_bits(const rpt_bf* bf, const rpt_key_column* col, const uint32_
   return probe_phase1_impl(bf, col, row_sel, n, workspace, workspace_bytes, stream, nullptr, nullptr, &done, out_bits);
 }
 
+// The default phase-2 tail: result bits + per-segment counts -> group sums -> their scan (and the count) -> the
+// ascending selection vector.
+static int launch_sel_tail(hipStream_t s, const uint64_t* bits, const uint32_t* seg_counts, uint32_t* group_sums,
+                           uint32_t* group_offs, uint64_t n_segs, const uint32_t* row_sel, uint32_t* out_sel,
+                           uint64_t* out_count_dev) {
+  const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
+  ProfScope prof8_("group_sum_kernel", s);
+  hipLaunchKernelGGL(rpt::group_sum_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
+                     seg_counts, n_segs, group_sums);
+  prof8_.end();
+  RPT_LAUNCHED("group_sum_kernel");
+  ProfScope prof9_("group_scan_kernel", s);
+  hipLaunchKernelGGL(rpt::group_scan_kernel, dim3(1), dim3(1024), 0, s, group_sums, static_cast<uint32_t>(n_groups),
+                     group_offs, out_count_dev);
+  prof9_.end();
+  RPT_LAUNCHED("group_scan_kernel");
+  ProfScope prof10_("compact_kernel", s);
+  hipLaunchKernelGGL(rpt::compact_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s, bits,
+                     seg_counts, n_segs, group_offs, row_sel, out_sel);
+  prof10_.end();
+  RPT_LAUNCHED("compact_kernel");
+  return RPT_OK;
+}
+
 int rpt_bf_probe_phase2(const rpt_bf* bf, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
                         uint64_t* out_count_dev, void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
   if (!bf || !out_count_dev) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
@@ -1666,22 +1736,7 @@ int rpt_bf_probe_phase2(const rpt_bf* bf, const uint32_t* row_sel, uint64_t n, u
     RPT_LAUNCHED("compact_kernel");
     return RPT_OK;
   }
-  ProfScope prof8_("group_sum_kernel", s);
-  hipLaunchKernelGGL(rpt::group_sum_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
-                     ws.seg_counts, n_segs, ws.group_sums);
-  prof8_.end();
-  RPT_LAUNCHED("group_sum_kernel");
-  ProfScope prof9_("group_scan_kernel", s);
-  hipLaunchKernelGGL(rpt::group_scan_kernel, dim3(1), dim3(1024), 0, s, ws.group_sums,
-                     static_cast<uint32_t>(n_groups), ws.group_offs, out_count_dev);
-  prof9_.end();
-  RPT_LAUNCHED("group_scan_kernel");
-  ProfScope prof10_("compact_kernel", s);
-  hipLaunchKernelGGL(rpt::compact_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
-                     ws.bits, ws.seg_counts, n_segs, ws.group_offs, row_sel, out_sel);
-  prof10_.end();
-  RPT_LAUNCHED("compact_kernel");
-  return RPT_OK;
+  return launch_sel_tail(s, ws.bits, ws.seg_counts, ws.group_sums, ws.group_offs, n_segs, row_sel, out_sel, out_count_dev);
 }
 
 int rpt_bf_probe_is_fused(const rpt_bf* bf, uint64_t n_rows) {
@@ -1747,6 +1802,152 @@ int rpt_bf_probe_chain(const rpt_bf* const* filters, const rpt_key_column* cols,
   prof.end();
   RPT_LAUNCHED("probe_chain_small_kernel");
   return RPT_OK;
+}
+
+// ---- the chain for batches of any size ---------------------------------------------------------------------
+// Workspace (all 256-aligned): accumulated result bits | their per-segment counts | the tail's group sums | group
+// offsets | one temporary bits array (only when a stage i >= 1 is PARTITIONED / BUCKETED) | the largest per-stage
+// probe workspace over the filters (workspace_layout of each filter's strategy for n rows).
+namespace {
+struct ChainWorkspace {
+  uint64_t* bits;
+  uint32_t* seg_counts;
+  uint32_t* group_sums;
+  uint32_t* group_offs;
+  uint64_t* tmp_bits;
+  void* stage;
+  size_t stage_bytes;
+};
+bool routed(int strategy) { return strategy == RPT_PROBE_PARTITIONED || strategy == RPT_PROBE_BUCKETED; }
+size_t chain_workspace_layout(const rpt_bf* const* filters, uint32_t k, uint64_t n, void* base, ChainWorkspace* ws) {
+  const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
+  const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
+  size_t stage = 0;
+  bool tmp = false;
+  for (uint32_t f = 0; f < k; f++) {
+    const int L = filters[f]->log_num_blocks;
+    const int st = resolve_strategy(filters[f]->probe_strategy.load(), L, n);
+    stage = std::max(stage, workspace_layout(n, L, st, nullptr, nullptr));
+    tmp = tmp || (f > 0 && routed(st));
+  }
+  constexpr int kParts = 6;
+  const size_t sz[kParts] = {align256(n_segs * rpt::kWordsPerSeg * 8), align256(n_groups * rpt::kGroupSegs * 4),
+                             align256(n_groups * 4), align256(n_groups * 4),
+                             tmp ? align256(n_segs * rpt::kWordsPerSeg * 8) : 0, stage};
+  size_t off[kParts], total = 0;
+  for (int i = 0; i < kParts; i++) {
+    off[i] = total;
+    total += sz[i];
+  }
+  if (ws) {
+    char* p = static_cast<char*>(base);
+    ws->bits = reinterpret_cast<uint64_t*>(p + off[0]);
+    ws->seg_counts = reinterpret_cast<uint32_t*>(p + off[1]);
+    ws->group_sums = reinterpret_cast<uint32_t*>(p + off[2]);
+    ws->group_offs = reinterpret_cast<uint32_t*>(p + off[3]);
+    ws->tmp_bits = sz[4] ? reinterpret_cast<uint64_t*>(p + off[4]) : nullptr;
+    ws->stage = p + off[5];
+    ws->stage_bytes = sz[5];
+  }
+  return total;
+}
+int check_chain_filters(const rpt_bf* const* filters, uint32_t n_filters) {
+  if (!filters) return fail(RPT_ERR_INVALID_ARGUMENT, "null filters");
+  if (n_filters == 0 || n_filters > RPT_MAX_CHAIN)
+    return fail(RPT_ERR_INVALID_ARGUMENT, "n_filters=%u outside 1..%d", n_filters, RPT_MAX_CHAIN);
+  for (uint32_t f = 0; f < n_filters; f++) {
+    if (!filters[f]) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter %u", f);
+    if (filters[f]->device != filters[0]->device) return fail(RPT_ERR_INVALID_ARGUMENT, "filters on different devices");
+  }
+  return RPT_OK;
+}
+}  // namespace
+
+size_t rpt_bf_probe_chain_workspace_bytes(const rpt_bf* const* filters, uint32_t n_filters, uint64_t n_rows) {
+  if (check_chain_filters(filters, n_filters) != RPT_OK) return 0;
+  if (n_rows >= (1ULL << 32)) {
+    fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n_rows);
+    return 0;
+  }
+  return chain_workspace_layout(filters, n_filters, n_rows, nullptr, nullptr);
+}
+
+int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                          const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                          void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  if (!filters || !cols || !out_count_dev) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
+  int st = check_chain_filters(filters, n_filters);
+  if (st != RPT_OK) return st;
+  if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
+  int strategy[RPT_MAX_CHAIN];
+  bool all_auto = true;
+  for (uint32_t f = 0; f < n_filters; f++) {
+    st = check_col(&cols[f]);
+    if (st != RPT_OK) return st;
+    const int L = filters[f]->log_num_blocks, requested = filters[f]->probe_strategy.load();
+    all_auto = all_auto && requested == RPT_PROBE_AUTO;
+    strategy[f] = resolve_strategy(requested, L, n);
+    if (!strategy_supported(strategy[f], L))
+      return fail(RPT_ERR_INVALID_ARGUMENT, "probe strategy %d unsupported for a 2^%d-block filter (filter %u)", strategy[f],
+                  L, f);
+  }
+  const int device = filters[0]->device;
+  RPT_ON_DEVICE(device);
+  hipStream_t s = as_stream(stream);
+  if (n == 0) {
+    RPT_HIP(hipMemsetAsync(out_count_dev, 0, sizeof(uint64_t), s));
+    return RPT_OK;
+  }
+  if (!out_sel) return fail(RPT_ERR_INVALID_ARGUMENT, "null out_sel");
+  const size_t need = chain_workspace_layout(filters, n_filters, n, nullptr, nullptr);
+  if (!workspace || workspace_bytes < need)
+    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
+  // a DuckDB-sized batch with nothing forced: the one-launch chain kernel (the workspace stays untouched)
+  if (n <= rpt::kSmallRows && all_auto)
+    return rpt_bf_probe_chain(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, stream);
+  for (uint32_t f = 0; f < n_filters; f++) RPT_SETTLE(filters[f], s);
+  ChainWorkspace ws;
+  chain_workspace_layout(filters, n_filters, n, workspace, &ws);
+  const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
+  // stage 0: the filter's own phase 1 (the PARTITIONED one ending in result bits) into the accumulated bits and counts
+  bool done = false;
+  st = probe_phase1_impl(filters[0], &cols[0], row_sel, n, ws.stage, ws.stage_bytes, stream, nullptr, nullptr, &done,
+                         ws.bits, ws.seg_counts);
+  if (st != RPT_OK) return st;
+  for (uint32_t f = 1; f < n_filters; f++) {
+    const rpt_bf* bf = filters[f];
+    const rpt_key_column* col = &cols[f];
+    if (routed(strategy[f])) {
+      // the whole batch through the stage's phase 1 (dead rows are partitioned too: routing only the survivors
+      // would need their count on the host), then one AND + recount
+      st = probe_phase1_impl(bf, col, row_sel, n, ws.stage, ws.stage_bytes, stream, nullptr, nullptr, &done, ws.tmp_bits);
+      if (st != RPT_OK) return st;
+      const uint64_t n_units = n_segs * (rpt::kWordsPerSeg / 2);
+      const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(
+          1, std::min<uint64_t>(ceil_div(n_units, rpt::kBlockThreads), static_cast<uint64_t>(num_cus(device)) * rpt::kBlocksPerCU)));
+      ProfScope prof("bits_and_count_kernel", s);
+      hipLaunchKernelGGL(rpt::bits_and_count_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, s, ws.bits, ws.tmp_bits,
+                         n_segs, ws.seg_counts);
+      prof.end();
+      RPT_LAUNCHED("bits_and_count_kernel");
+      continue;
+    }
+    const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
+    const bool dense = dense_ok(col, row_sel);
+    if (strategy[f] == RPT_PROBE_GATHER) {
+      const unsigned grid = persistent_grid(device, n_segs);
+      RPT_DISPATCH_KD(launch_probe_bits_masked_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
+      RPT_LAUNCHED("probe_bits_masked_kernel");
+    } else {  // RPT_PROBE_LDS
+      const unsigned grid = lds_probe_grid(device, bf->log_num_blocks, n_segs);
+      RPT_DISPATCH_KD(launch_probe_bits_masked_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits,
+                      ws.seg_counts);
+      RPT_LAUNCHED("probe_bits_masked_kernel<lds>");
+    }
+  }
+  // the tail, once
+  return launch_sel_tail(s, ws.bits, ws.seg_counts, ws.group_sums, ws.group_offs, n_segs, row_sel, out_sel, out_count_dev);
 }
 
 

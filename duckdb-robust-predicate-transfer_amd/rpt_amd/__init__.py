@@ -30,6 +30,8 @@ from .bloom import (  # noqa: F401
     make_column,
     needs_resize,
     probe_chain,
+    probe_chain_workspace_bytes,
+    probe_chain_ws,
     synth_build_keys,
     synth_probe_keys,
     validity_from_mask,

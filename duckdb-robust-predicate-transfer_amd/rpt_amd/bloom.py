@@ -77,6 +77,50 @@ def probe_chain(filters, columns, *, row_sel: Optional[torch.Tensor] = None, n: 
     return out_sel[: int(out_count.item())]
 
 
+def probe_chain_workspace_bytes(filters, n: int) -> int:
+    """Device workspace probe_chain_ws needs for these filters (their strategies resolved for n) and n rows
+    (rpt_bf_probe_chain_workspace_bytes)."""
+    if not filters:
+        raise RptError(1, "at least one filter")
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    return int(filters[0]._lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), int(n)))
+
+
+def probe_chain_ws(filters, columns, *, row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                   out_sel: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """probe_chain for batches of any size (rpt_bf_probe_chain_ws): the survivors stay on the device as result
+    bits between the filters, each filter runs its own probe strategy, and the selection vector is written once
+    at the end. Arguments as probe_chain, plus a device workspace of probe_chain_workspace_bytes(filters, n) bytes
+    (allocated here when None). Returns out_sel[:count] (reads the count back)."""
+    if not filters or len(filters) != len(columns):
+        raise RptError(1, "one key column per filter, at least one filter")
+    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
+    if n is None:
+        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
+        n = (row_sel.numel() if row_sel is not None else
+             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
+    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+        raise RptError(1, "row_sel must be a 32-bit device tensor")
+    device = filters[0].device
+    lib = filters[0]._lib
+    if out_sel is None:
+        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    if out_count is None:
+        out_count = torch.zeros(1, dtype=torch.int64, device=device)
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    if workspace is None:
+        need = int(lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            workspace.record_stream(stream)  # freed on return while the chain may still run on `stream`
+    arr = (KeyColumn * len(cols))(*cols)
+    check(lib.rpt_bf_probe_chain_ws(handles, arr, len(filters), _ptr(row_sel), n, out_sel.data_ptr(),
+                                    out_count.data_ptr(), workspace.data_ptr(),
+                                    workspace.numel() * workspace.element_size(), _stream(device, stream)), lib)
+    return out_sel[: int(out_count.item())]
+
+
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,
                 validity: Optional[torch.Tensor] = None) -> KeyColumn:
     """rpt_key_column for a FLAT (key_sel None) or DICTIONARY (key_sel uint32/int32) key vector."""

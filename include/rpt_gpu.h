@@ -248,6 +248,41 @@ int rpt_bf_probe(const rpt_bf* bf, const rpt_key_column* col, const uint32_t* ro
 int rpt_bf_probe_chain(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
                        const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
                        rpt_stream_t stream);
+/* rpt_bf_probe_chain for batches of any size (n < 2^32): same arguments, same result (ascending ids of the
+ * rows that pass every filters[i] on cols[i]; *out_count_dev their count), plus a caller workspace. What a
+ * device-resident USE_BF calls for a large batch instead of one rpt_bf_probe per filter with the count read
+ * back in between.
+ * Filters and columns: 1..RPT_MAX_CHAIN filters, all on one device; each column has its own key type (I64 / I32 /
+ *   HASH), dictionary and validity; row_sel works as in rpt_bf_probe (every filter probes rows row_sel[0..n), the
+ *   ids written are the row_sel values). The result equals the reference loop's (each LookupSel over the previous
+ *   survivors) and does not depend on the order of the filters.
+ * Ordering and capture: fully stream-ordered: no host synchronisation, no device-to-host copy, no allocation. It
+ *   captures into a stream capture under the rules of rpt_bf_probe (rpt_bf_settle above): every filter's deferred
+ *   clear is settled first, as rpt_bf_probe_chain does, so a pending one is refused inside a capture with
+ *   RPT_ERR_INVALID_ARGUMENT before anything is enqueued.
+ * Strategies: filter i runs the strategy rpt_bf_probe_strategy_for(filters[i], n) reports (rpt_bf_set_probe_strategy
+ *   is honoured per filter). The survivors stay on the device as result bits (the layout of rpt_bf_probe_bits) plus
+ *   one count per 512-row segment: filter 0 runs its phase 1 into them; a later GATHER / LDS filter runs a masked
+ *   probe over them in place (a 512-row segment with no survivor loads no key and touches no filter word; a dead
+ *   row of a live segment makes no global gather); a later PARTITIONED / BUCKETED filter runs its phase 1 over all
+ *   n rows into a temporary bits array, which is then ANDed in (dead rows are partitioned too: routing only the
+ *   survivors would need their count on the host); one phase 2 at the end writes out_sel and the count.
+ *   When 1 <= n <= RPT_SMALL_PROBE_ROWS and every filter is on RPT_PROBE_AUTO the call hands over to
+ *   rpt_bf_probe_chain's one-launch kernel and leaves the workspace untouched; with any strategy forced it takes
+ *   the path above even at n = 1.
+ * Caller buffers ("Caller buffers" at the top): the workspace may hold anything on entry; exactly
+ *   rpt_bf_probe_chain_workspace_bytes(filters, n_filters, n) bytes are enough, as are out_sel of exactly n entries
+ *   and out_count_dev of one uint64; nothing outside these is written. A workspace that is not 16-byte aligned
+ *   returns RPT_ERR_INVALID_ARGUMENT, one that is too small RPT_ERR_WORKSPACE, both before any launch.
+ * Edge cases: n == 0 sets the count to 0 (stream-ordered) and does nothing else. n >= 2^32, n_filters outside
+ *   1..RPT_MAX_CHAIN, a null filter or column, a null out_sel with n > 0, or filters on different devices return
+ *   RPT_ERR_INVALID_ARGUMENT. An empty filter passes nothing (its words are zero).
+ * rpt_bf_probe_chain_workspace_bytes: the device workspace these filters (their strategies resolved for n_rows) and
+ *   n_rows rows need; 256-aligned; 0 on a null / invalid argument. Host-only. */
+size_t rpt_bf_probe_chain_workspace_bytes(const rpt_bf* const* filters, uint32_t n_filters, uint64_t n_rows);
+int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                          const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                          void* workspace, size_t workspace_bytes, rpt_stream_t stream);
 /* rpt_bf_probe in its two stream-ordered phases (same filter, workspace and stream), for callers that
  * time or overlap them. GATHER / LDS: phase 1 = hash + gather + result bits + per-segment counts,
  * phase 2 = scan + expansion into out_sel. PARTITIONED: phase 1 = partition rows by filter slice +
