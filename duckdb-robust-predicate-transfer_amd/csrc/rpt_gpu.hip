@@ -16,6 +16,9 @@
 //             phase 2 = two-level scan + expansion into an ascending uint32 sel (compaction.hpp).
 //   insert  : atomic OR per key (misc.hpp), or the partitioned / bucketed routing with the slices
 //             ORed in LDS; the build's key min/max is folded in on the way.
+//             rows chosen on the device (result bits, or a selection vector with a device-side count:
+//             insert_masked.hpp): atomic ORs of a probe's survivors, no count on the host.
+//   transfer: rpt_bf_transfer_ws = the filter chain, then its survivors inserted into the outgoing filters.
 //   merge   : OR of partial filters / peer slices;  fold;  popcount (misc.hpp).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -48,6 +51,7 @@
 #include "kernels/bucketed.hpp"
 #include "kernels/compaction.hpp"
 #include "kernels/misc.hpp"
+#include "kernels/insert_masked.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_FUSED_SEL
@@ -914,6 +918,24 @@ void launch_insert_t(unsigned grid, hipStream_t s, rpt_bf* bf, const rpt::KeyArg
   prof.end();
 }
 
+// The inserts whose rows are chosen on the device (insert_masked.hpp).
+template <int K, bool D>
+void launch_insert_bits_t(unsigned grid, hipStream_t s, rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n, uint64_t n_segs,
+                          const uint64_t* bits) {
+  ProfScope prof(inst_name<K, D>("insert_bits_kernel"), s);
+  hipLaunchKernelGGL((rpt::insert_bits_kernel<K, D>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
+                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, bf->stats);
+  prof.end();
+}
+template <int K, bool D>  // D unused: a selection vector is always the general mapping
+void launch_insert_sel_t(unsigned grid, hipStream_t s, rpt_bf* bf, const rpt::KeyArgs& a, const uint64_t* count_dev,
+                         uint64_t max_rows) {
+  ProfScope prof(inst_name<K>("insert_sel_kernel"), s);
+  hipLaunchKernelGGL((rpt::insert_sel_kernel<K>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
+                     (1ULL << bf->log_num_blocks) - 1, a, count_dev, max_rows, bf->stats);
+  prof.end();
+}
+
 template <int K, bool D>
 void launch_bucket_scatter_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t bucket_mask,
                              const rpt::L1Lists& lists, uint32_t* hash_lo, uint8_t* hash_hi, uint16_t* pos1,
@@ -1320,6 +1342,57 @@ int rpt_bf_insert(rpt_bf* bf, const rpt_key_column* col, uint64_t n, rpt_stream_
   order.done(false);
   RPT_LAUNCHED("insert_kernel");
   return RPT_OK;
+}
+
+// The write scope of rpt_bf_insert around an insert whose rows are chosen on the device (insert_masked.hpp):
+// bits != nullptr: rows i < n (row i, or sel[i]) whose bit is set; else rows sel[0 .. min(*count_dev, n)).
+// The caller has validated the arguments, made the filter's device current and run RPT_REFUSE_CAPTURE_WRITE.
+// n > 0. has_data becomes 1 whatever the device-side selection holds: the host cannot know it was empty.
+static int enqueue_device_rows_insert(rpt_bf* bf, const rpt_key_column* col, const uint64_t* bits, const uint32_t* sel,
+                                      const uint64_t* count_dev, uint64_t n, hipStream_t s) {
+  bf->has_data.store(1);
+  const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
+  const unsigned grid = persistent_grid(bf->device, n_segs);
+  const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, sel};
+  WriteOrder order(bf, s);
+  RPT_REFUSE_IN_FLIGHT(order, "write");
+  const hipError_t ez = zero_pending_locked(bf, s);
+  if (ez != hipSuccess) return fail(RPT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez));
+  if (bits != nullptr)
+    RPT_DISPATCH_KD(launch_insert_bits_t, col->key_type, dense_ok(col, sel), grid, s, bf, a, n, n_segs, bits);
+  else
+    RPT_DISPATCH_KD(launch_insert_sel_t, col->key_type, false, grid, s, bf, a, count_dev, n);
+  order.done(false);
+  RPT_LAUNCHED(bits != nullptr ? "insert_bits_kernel" : "insert_sel_kernel");
+  return RPT_OK;
+}
+
+int rpt_bf_insert_bits(rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
+                       const uint64_t* row_bits, rpt_stream_t stream) {
+  if (!bf) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter");
+  if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
+  if (n == 0) return RPT_OK;
+  int st = check_col(col);
+  if (st != RPT_OK) return st;
+  if (!row_bits) return fail(RPT_ERR_INVALID_ARGUMENT, "null row_bits");
+  RPT_ON_DEVICE(bf->device);
+  RPT_REFUSE_CAPTURE_WRITE(bf, as_stream(stream), "insert");
+  return enqueue_device_rows_insert(bf, col, row_bits, row_sel, nullptr, n, as_stream(stream));
+}
+
+int rpt_bf_insert_sel(rpt_bf* bf, const rpt_key_column* col, const uint32_t* sel, const uint64_t* count_dev,
+                      uint64_t max_rows, rpt_stream_t stream) {
+  if (!bf) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter");
+  if (max_rows >= (1ULL << 32))
+    return fail(RPT_ERR_INVALID_ARGUMENT, "max_rows=%llu rows exceeds uint32 sel_t", (unsigned long long)max_rows);
+  if (max_rows == 0) return RPT_OK;
+  int st = check_col(col);
+  if (st != RPT_OK) return st;
+  if (!sel) return fail(RPT_ERR_INVALID_ARGUMENT, "null sel");
+  if (!count_dev) return fail(RPT_ERR_INVALID_ARGUMENT, "null count_dev");
+  RPT_ON_DEVICE(bf->device);
+  RPT_REFUSE_CAPTURE_WRITE(bf, as_stream(stream), "insert");
+  return enqueue_device_rows_insert(bf, col, nullptr, sel, count_dev, max_rows, as_stream(stream));
 }
 
 size_t rpt_insert_workspace_bytes(uint64_t n_rows, int log_num_blocks) {
@@ -1872,9 +1945,14 @@ size_t rpt_bf_probe_chain_workspace_bytes(const rpt_bf* const* filters, uint32_t
   return chain_workspace_layout(filters, n_filters, n_rows, nullptr, nullptr);
 }
 
-int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
-                          const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
-                          void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+// The body of rpt_bf_probe_chain_ws, shared with rpt_bf_transfer_ws. *survivor_bits (nullable) tells the caller where
+// the survivors are once the call is enqueued: the accumulated result bits in the workspace (the workspace path), or
+// nullptr when only out_sel / *out_count_dev hold them (the small-batch hand-over) or nothing was probed (n == 0).
+static int probe_chain_ws_impl(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                               const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                               void* workspace, size_t workspace_bytes, rpt_stream_t stream,
+                               const uint64_t** survivor_bits) {
+  if (survivor_bits) *survivor_bits = nullptr;
   if (!filters || !cols || !out_count_dev) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
   int st = check_chain_filters(filters, n_filters);
   if (st != RPT_OK) return st;
@@ -1946,8 +2024,64 @@ int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* co
       RPT_LAUNCHED("probe_bits_masked_kernel<lds>");
     }
   }
+  if (survivor_bits) *survivor_bits = ws.bits;
   // the tail, once
   return launch_sel_tail(s, ws.bits, ws.seg_counts, ws.group_sums, ws.group_offs, n_segs, row_sel, out_sel, out_count_dev);
+}
+
+int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                          const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                          void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  return probe_chain_ws_impl(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, workspace, workspace_bytes,
+                             stream, nullptr);
+}
+
+int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                       rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                       const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                       void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  if (!filters || !cols || !out_count_dev || !dst_filters || !dst_cols)
+    return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_filters == 0 || n_filters > RPT_MAX_CHAIN)
+    return fail(RPT_ERR_INVALID_ARGUMENT, "n_filters=%u outside 1..%d", n_filters, RPT_MAX_CHAIN);
+  if (n_dst == 0 || n_dst > RPT_MAX_CHAIN)
+    return fail(RPT_ERR_INVALID_ARGUMENT, "n_dst=%u outside 1..%d", n_dst, RPT_MAX_CHAIN);
+  // handles are compared before any of them is looked into
+  for (uint32_t f = 0; f < n_filters; f++)
+    if (!filters[f]) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter %u", f);
+  for (uint32_t j = 0; j < n_dst; j++) {
+    if (!dst_filters[j]) return fail(RPT_ERR_INVALID_ARGUMENT, "null destination filter %u", j);
+    for (uint32_t f = 0; f < n_filters; f++)
+      if (dst_filters[j] == filters[f])
+        return fail(RPT_ERR_INVALID_ARGUMENT, "destination filter %u is probed filter %u of the same call", j, f);
+  }
+  int st = check_chain_filters(filters, n_filters);
+  if (st != RPT_OK) return st;
+  if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
+  const int device = filters[0]->device;
+  for (uint32_t j = 0; j < n_dst; j++) {
+    if (dst_filters[j]->device != device)
+      return fail(RPT_ERR_INVALID_ARGUMENT, "destination filter %u is not on the chain's device", j);
+    st = check_col(&dst_cols[j]);
+    if (st != RPT_OK) return st;
+  }
+  RPT_ON_DEVICE(device);
+  hipStream_t s = as_stream(stream);
+  // every destination's capture and in-flight check before the chain enqueues anything (n == 0 writes none)
+  if (n > 0)
+    for (uint32_t j = 0; j < n_dst; j++) RPT_REFUSE_CAPTURE_WRITE(dst_filters[j], s, "transfer");
+  const uint64_t* bits = nullptr;
+  st = probe_chain_ws_impl(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, workspace, workspace_bytes,
+                           stream, &bits);
+  if (st != RPT_OK || n == 0) return st;
+  // the survivors into the outgoing filters: from the accumulated bits (rows row_sel[i] of dst_cols[j], as probed),
+  // or, after the hand-over, from out_sel, which holds the same row ids
+  for (uint32_t j = 0; j < n_dst; j++) {
+    st = bits != nullptr ? enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, s)
+                         : enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], nullptr, out_sel, out_count_dev, n, s);
+    if (st != RPT_OK) return st;
+  }
+  return RPT_OK;
 }
 
 

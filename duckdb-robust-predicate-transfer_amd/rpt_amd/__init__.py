@@ -34,6 +34,7 @@ from .bloom import (  # noqa: F401
     probe_chain_ws,
     synth_build_keys,
     synth_probe_keys,
+    transfer_ws,
     validity_from_mask,
     words_or_slices,
 )

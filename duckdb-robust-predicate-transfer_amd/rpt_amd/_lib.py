@@ -118,6 +118,13 @@ SIGNATURES = {
         c_int,
         [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "rpt_bf_insert_bits": (c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_void_p]),
+    "rpt_bf_insert_sel": (c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_void_p, c_uint64, c_void_p]),
+    "rpt_bf_transfer_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "rpt_bf_probe_phase1": (
         c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_size_t, c_void_p]
     ),

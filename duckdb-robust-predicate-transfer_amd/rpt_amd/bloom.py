@@ -121,6 +121,48 @@ def probe_chain_ws(filters, columns, *, row_sel: Optional[torch.Tensor] = None, 
     return out_sel[: int(out_count.item())]
 
 
+def transfer_ws(filters, columns, dst_filters, dst_columns, *, row_sel: Optional[torch.Tensor] = None,
+                n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+                out_count: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, stream=None):
+    """One USE_BF -> CREATE_BF step on the device (rpt_bf_transfer_ws): probe_chain_ws over filters / columns,
+    then the survivors inserted into dst_filters[j] on its own key column dst_columns[j]. Nothing is read back:
+    returns the device tensors (out_sel, out_count), the count not synchronized (out_sel[:int(out_count)] are
+    the survivors once the stream has run). Columns as in probe_chain; the destination columns are indexed by
+    the same row ids as the probed ones. A destination's is_empty() is False afterwards even if no row survived
+    (set_has_data(False) restores it once a zero count has been read)."""
+    if not filters or len(filters) != len(columns):
+        raise RptError(1, "one key column per filter, at least one filter")
+    if not dst_filters or len(dst_filters) != len(dst_columns):
+        raise RptError(1, "one key column per destination filter, at least one destination")
+    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
+    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
+    if n is None:
+        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
+        n = (row_sel.numel() if row_sel is not None else
+             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
+    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+        raise RptError(1, "row_sel must be a 32-bit device tensor")
+    device = filters[0].device
+    lib = filters[0]._lib
+    if out_sel is None:
+        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    if out_count is None:
+        out_count = torch.zeros(1, dtype=torch.int64, device=device)
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
+    if workspace is None:
+        need = int(lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            workspace.record_stream(stream)  # freed on return while the transfer may still run on `stream`
+    arr = (KeyColumn * len(cols))(*cols)
+    darr = (KeyColumn * len(dcols))(*dcols)
+    check(lib.rpt_bf_transfer_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters), _ptr(row_sel), n,
+                                 out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
+                                 workspace.numel() * workspace.element_size(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,
                 validity: Optional[torch.Tensor] = None) -> KeyColumn:
     """rpt_key_column for a FLAT (key_sel None) or DICTIONARY (key_sel uint32/int32) key vector."""
@@ -288,6 +330,41 @@ class BloomFilter:
                                              _stream(self.device, stream)))
         else:
             check(self._lib.rpt_bf_insert(self._h, ctypes.byref(col), n, _stream(self.device, stream)))
+
+    def insert_bits(self, keys: torch.Tensor, bits: torch.Tensor, *, n: Optional[int] = None,
+                    row_sel: Optional[torch.Tensor] = None, key_type: Optional[int] = None, key_sel=None,
+                    validity=None, stream=None) -> None:
+        """Insert the rows i < n (row i, or row_sel[i]) whose bit i is set in `bits` (rpt_bf_insert_bits): 64-bit
+        device words in the layout of rpt_bf_probe_bits, ceil(n / 512) * 8 of them; bits past n are ignored.
+        Stream-ordered, nothing is read back; is_empty() is False afterwards whatever the bits held."""
+        if n is None:
+            n = row_sel.numel() if row_sel is not None else (key_sel.numel() if key_sel is not None else keys.numel())
+        col = make_column(keys, key_type, key_sel, validity)
+        if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+            raise RptError(1, "row_sel must be a 32-bit device tensor")
+        need = ((n + SEG_ROWS - 1) // SEG_ROWS) * (SEG_ROWS // 64)
+        if not bits.is_cuda or not bits.is_contiguous() or bits.element_size() != 8 or bits.numel() < need:
+            raise RptError(1, f"bits must be a contiguous device tensor of at least {need} 64-bit words")
+        check(self._lib.rpt_bf_insert_bits(self._h, ctypes.byref(col), _ptr(row_sel), n, bits.data_ptr(),
+                                           _stream(self.device, stream)), self._lib)
+
+    def insert_sel(self, keys: torch.Tensor, sel: torch.Tensor, count: torch.Tensor, *,
+                   max_rows: Optional[int] = None, key_type: Optional[int] = None, key_sel=None, validity=None,
+                   stream=None) -> None:
+        """Insert rows sel[0 .. min(count, max_rows)) (rpt_bf_insert_sel): `sel` a 32-bit device tensor of row ids,
+        `count` a one-element 64-bit device tensor read when the kernel runs (what probe_async returns), max_rows
+        the capacity of sel (default: its length). Stream-ordered, nothing is read back; is_empty() is False
+        afterwards whatever the count held."""
+        col = make_column(keys, key_type, key_sel, validity)
+        if not sel.is_cuda or not sel.is_contiguous() or sel.element_size() != 4:
+            raise RptError(1, "sel must be a contiguous 32-bit device tensor")
+        if not count.is_cuda or count.element_size() != 8 or count.numel() < 1:
+            raise RptError(1, "count must be a 64-bit device tensor")
+        max_rows = sel.numel() if max_rows is None else int(max_rows)
+        if max_rows > sel.numel():
+            raise RptError(1, f"max_rows={max_rows} exceeds the {sel.numel()} entries of sel")
+        check(self._lib.rpt_bf_insert_sel(self._h, ctypes.byref(col), sel.data_ptr(), count.data_ptr(), max_rows,
+                                          _stream(self.device, stream)), self._lib)
 
     def reinitialize(self, actual_rows: int) -> None:
         check(self._lib.rpt_bf_reinitialize(self._h, int(actual_rows)))
@@ -486,6 +563,7 @@ __all__: Sequence[str] = [
     "BloomFilter",
     "ProbeWorkspace",
     "make_column",
+    "transfer_ws",
     "validity_from_mask",
     "hash_keys",
     "hash_columns",

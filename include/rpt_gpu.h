@@ -320,6 +320,50 @@ int rpt_hash_combine(const rpt_key_column* col, uint64_t n, uint64_t* inout_hash
 int rpt_keys_widen(const uint32_t* lo, const uint32_t* chunk_hi, const uint32_t* chunk_row0, uint64_t n_chunks,
                    uint64_t* out, rpt_stream_t stream);
 
+/* ---- transfer: a probe's survivors into the next filter, on the device --------------------------- */
+/* Predicate transfer chains the two halves: a table is reduced by the filters that reach it (USE_BF,
+ * physical_use_bf.cpp:127-179), and the rows that survive are inserted into the filter the table sends on
+ * (CREATE_BF's Sink, physical_create_bf.cpp:201-242; PTBloomFilter::Insert, bloom_filter.cpp:70-78). The probes
+ * above leave their survivors on the device (result bits, or out_sel and *out_count_dev); these inserts take their
+ * row set from there, so the step needs no synchronisation and no count on the host, and captures into a graph.
+ *
+ * rpt_bf_insert_bits: insert the rows i < n of col (row i, or row_sel[i]) whose bit i is set in row_bits (the
+ *   layout of rpt_bf_probe_bits: ceil(n/512)*8 words of device memory, LSB first; bits at positions >= n are
+ *   ignored). A 512-row segment without a set bit loads no key.
+ * rpt_bf_insert_sel: insert rows sel[0 .. min(*count_dev, max_rows)) of col. The count is read on the device when
+ *   the kernel runs (what rpt_bf_probe / rpt_bf_probe_chain[_ws] left in *out_count_dev, earlier on the stream);
+ *   max_rows is the capacity of sel (it sizes the launch and clamps the count); no sel entry at or past the clamped
+ *   count is read. sel holds row ids of col (dictionary columns: key_sel[sel[i]]).
+ * rpt_bf_transfer_ws: rpt_bf_probe_chain_ws(filters, cols, ..., out_sel, out_count_dev, workspace), then the
+ *   survivors inserted into dst_filters[j] on its own key column dst_cols[j], j < n_dst (1..RPT_MAX_CHAIN
+ *   destinations). Arguments, result and workspace (rpt_bf_probe_chain_workspace_bytes; the inserts need none) are
+ *   rpt_bf_probe_chain_ws's. On the workspace path the destinations are fed from the accumulated result bits, on
+ *   the small-batch hand-over (n <= RPT_SMALL_PROBE_ROWS, every probed filter on AUTO) from out_sel and the count;
+ *   either way row row_sel[i] (or i) of dst_cols[j] is inserted iff it passed every probed filter. Every
+ *   destination must be on the chain's device and none may be one of filters[] (RPT_ERR_INVALID_ARGUMENT); these
+ *   and the destinations' capture checks run before anything is enqueued. n == 0 sets the count to 0 and touches
+ *   no destination.
+ *
+ * All three: the filter ends up bit-identical to rpt_bf_insert of exactly the selected rows (ORed into what it
+ *   holds; the min/max of the selected valid I32/I64 keys folded in; a selected NULL row inserts NULL_HASH). One
+ *   atomic OR per row, whatever the filter's insert strategy: the routed inserts need their row count on the host.
+ *   Stream-ordered: no synchronisation, no copy back, no allocation. Writes follow rpt_bf_insert's rules
+ *   (rpt_bf_settle above): ordered after the filter's previous write; a deferred clear is settled first outside a
+ *   capture and refused inside one; a captured call ORs its rows at every replay.
+ * has_data becomes 1 whenever n / max_rows > 0, even if the selection turns out empty: the host cannot know. That
+ *   is result-neutral (an all-zero filter passes nothing); a caller that later reads a zero count may restore
+ *   IsEmpty with rpt_bf_set_has_data(bf, 0).
+ * n == 0 / max_rows == 0 is a no-op. A null filter, column, keys, row_bits, sel or count_dev, n or max_rows >= 2^32,
+ *   or a bad key type return RPT_ERR_INVALID_ARGUMENT before any launch. */
+int rpt_bf_insert_bits(rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
+                       const uint64_t* row_bits, rpt_stream_t stream);
+int rpt_bf_insert_sel(rpt_bf* bf, const rpt_key_column* col, const uint32_t* sel, const uint64_t* count_dev,
+                      uint64_t max_rows, rpt_stream_t stream);
+int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                       rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                       const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                       void* workspace, size_t workspace_bytes, rpt_stream_t stream);
+
 /* ---- merge / fold / export ----------------------------------------------------------------- */
 /* dst |= src (same log_num_blocks, same device): merging per-thread or per-GPU partial filters
  * built over disjoint row ranges gives the filter of the union, bit-identical to one build. */
