@@ -206,13 +206,20 @@ hipEvent_t prof_event() {
   return e;
 }
 
-// Brackets one kernel launch with events on its stream when profiling is enabled.
+bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// Brackets one kernel launch with events on its stream when profiling is enabled. Not on a capturing stream: an
+// event recorded there becomes a node of the graph and can never be timed (hipEventElapsedTime fails on it), so a
+// captured launch, and every replay of it, stays out of the record.
 struct ProfScope {
   const char* name;
   hipStream_t stream;
   hipEvent_t start = nullptr;
   ProfScope(const char* n, hipStream_t s) : name(n), stream(s) {
-    if (!g_prof_enabled.load(std::memory_order_relaxed)) return;
+    if (!g_prof_enabled.load(std::memory_order_relaxed) || stream_capturing(s)) return;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     start = prof_event();
     if (start && hipEventRecord(start, stream) != hipSuccess) start = nullptr;
@@ -252,11 +259,6 @@ const char* inst_name(const char* base) {
   s.back() = '>';
   names.emplace_back(base, std::move(s));
   return names.back().second.c_str();
-}
-
-bool stream_capturing(hipStream_t s) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 
 // Has `ev` (recorded outside any capture) completed, asked while the calling thread's stream is capturing?
@@ -2894,17 +2896,21 @@ int rpt_profiling_reset(void) {
 
 int rpt_profiling_read(rpt_kernel_stat* out, int capacity) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
+  // every pending record leaves the list exactly once, with its two events back in the free list exactly once: one
+  // whose events cannot be resolved is dropped (not counted), the rest are processed
   for (auto& r : g_prof_pending) {
     float ms = 0.f;
-    if (hipEventSynchronize(r.end) != hipSuccess || hipEventElapsedTime(&ms, r.start, r.end) != hipSuccess)
-      return -fail(RPT_ERR_HIP, "profiling: event query failed");
-    auto it = std::find_if(g_prof_stats.begin(), g_prof_stats.end(), [&](const auto& p) { return p.first == r.name; });
-    if (it == g_prof_stats.end()) {
-      g_prof_stats.push_back({std::string(r.name), ProfStat{}});
-      it = g_prof_stats.end() - 1;
+    if (hipEventSynchronize(r.end) == hipSuccess && hipEventElapsedTime(&ms, r.start, r.end) == hipSuccess) {
+      auto it = std::find_if(g_prof_stats.begin(), g_prof_stats.end(), [&](const auto& p) { return p.first == r.name; });
+      if (it == g_prof_stats.end()) {
+        g_prof_stats.push_back({std::string(r.name), ProfStat{}});
+        it = g_prof_stats.end() - 1;
+      }
+      it->second.launches++;
+      it->second.total_ms += ms;
+    } else {
+      (void)hipGetLastError();  // not left for the next launch check to report
     }
-    it->second.launches++;
-    it->second.total_ms += ms;
     g_prof_free.push_back(r.start);
     g_prof_free.push_back(r.end);
   }

@@ -472,7 +472,12 @@ int rpt_bf_set_has_data(rpt_bf* bf, int value);
 /* The reference's per-operator profiling counters (src/include/rpt_profiling.hpp:16-217), at kernel
  * granularity: while enabled, every kernel the library launches is bracketed by HIP events on its
  * own stream. rpt_profiling_read resolves pending events (waits for them), fills up to `capacity`
- * entries and returns the number of distinct kernels (negative status on error). */
+ * entries and returns the number of distinct kernels (negative status on error); out == NULL or
+ * capacity == 0 only counts. Names are the kernels' instantiation names ("partition_kernel<0,true,false,1,0>"),
+ * cut to 47 characters. Process-wide, thread-safe.
+ * Stream capture: a launch on a capturing stream is not recorded (events recorded into a graph cannot be
+ * timed), and neither are the graph's replays: the record holds the launches made outside captures only.
+ * A launch whose events cannot be resolved at read time is dropped from the record, the others are counted. */
 typedef struct rpt_kernel_stat {
   char name[48];
   uint64_t launches;
