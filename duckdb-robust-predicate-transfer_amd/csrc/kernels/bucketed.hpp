@@ -16,8 +16,8 @@ namespace rpt {
 // groups, so a list's neighbouring runs leave one L2 and merge there into whole lines; 1 group for
 // small batches, where 8 lists per bucket would pad too much). A list is a sequence of 4 Ki-row chunks: a
 // run's rows [p, p + c) of its list come from one returning atomic on the list's row cursor, whose
-// latency overlaps the LDS sort. The first K chunks of every list have fixed ids (list * K + c; K = 1 by
-// default, rpt_gpu.hip RPT_L1_FIXED_PCT). Beyond K a list grows by extents of kExtentChunks chunks
+// latency overlaps the LDS sort. The first K chunks of every list have fixed ids (list * K + c; K = 1,
+// rpt_gpu.hip l1_geom). Beyond K a list grows by extents of kExtentChunks chunks
 // taken from its group's pool shard (one atomic per 64 Ki rows of a list): the run that
 // covers an extent's first row takes it and publishes its first chunk id in ext_dir; a run that starts
 // inside an extent someone else took waits for that id (its taker did its cursor atomic earlier and
@@ -77,12 +77,9 @@ __device__ __forceinline__ void l1_flag_error(const L1Lists& L) {
   __hip_atomic_store(L.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The scatter's row map (pos_out) leaves as one 2V-byte store per lane for dense keys (1), non-temporal like
-// the partition's (2), or as V strided u16 stores (0): scatter 2.967-3.006 -> 2.940-2.969 ms with 2, C5 share
-// 8.47-8.52 -> 8.44-8.47 ms (profiles/r04/ab_scatter_pos_pack.txt).
-#ifndef RPT_SCATTER_POS_PACK
-#define RPT_SCATTER_POS_PACK 2
-#endif
+// The scatter's row map (pos_out) leaves as one 2V-byte store per lane for dense keys, non-temporal like the
+// partition's: against V strided u16 stores, scatter 2.967-3.006 -> 2.940-2.969 ms, C5 share 8.47-8.52 ->
+// 8.44-8.47 ms (profiles/r04/ab_scatter_pos_pack.txt).
 // B1: one pass over a 16 Ki-row level-1 tile: hash every row (held in registers), rank it within its
 // bucket (LDS atomic), append each bucket's run to its list (see above), sort the tile's hashes by
 // bucket in LDS and copy them to their list positions as the level-2 kKeySplit layout: hash bits 0..31
@@ -180,7 +177,7 @@ __global__ __launch_bounds__(kTileThreads) void bucket_scatter_kernel(KeyArgs a,
       pv[j] = static_cast<uint16_t>(p);
     }
     if (pos_out == nullptr) {  // padded to whole tiles: rows >= n get don't-care values
-    } else if constexpr (DENSE && RPT_SCATTER_POS_PACK) {
+    } else if constexpr (DENSE) {
       // a lane's V adjacent rows leave as one 2V-byte store (one coalesced 128 / 256-B piece per
       // instruction instead of V strided u16 stores that each half-fill their lines)
       constexpr int V = KeyTraits<K>::kVec;
@@ -188,13 +185,12 @@ __global__ __launch_bounds__(kTileThreads) void bucket_scatter_kernel(KeyArgs a,
       for (int c = 0; c < 8 / V; c++) {
         const uint64_t row0 = sbase + static_cast<uint64_t>(c) * 64 * V + static_cast<uint64_t>(lane) * V;
         if constexpr (V == 2) {
-          part_store<RPT_SCATTER_POS_PACK == 2>(reinterpret_cast<uint32_t*>(pos_out + row0),
-                                                static_cast<uint32_t>(pv[c * 2]) | (static_cast<uint32_t>(pv[c * 2 + 1]) << 16));
+          part_store<true>(reinterpret_cast<uint32_t*>(pos_out + row0),
+                           static_cast<uint32_t>(pv[c * 2]) | (static_cast<uint32_t>(pv[c * 2 + 1]) << 16));
         } else {
-          part_store<RPT_SCATTER_POS_PACK == 2>(reinterpret_cast<uint64_t*>(pos_out + row0),
-                                                static_cast<uint64_t>(pv[c * 4]) | (static_cast<uint64_t>(pv[c * 4 + 1]) << 16) |
-                                                    (static_cast<uint64_t>(pv[c * 4 + 2]) << 32) |
-                                                    (static_cast<uint64_t>(pv[c * 4 + 3]) << 48));
+          part_store<true>(reinterpret_cast<uint64_t*>(pos_out + row0),
+                           static_cast<uint64_t>(pv[c * 4]) | (static_cast<uint64_t>(pv[c * 4 + 1]) << 16) |
+                               (static_cast<uint64_t>(pv[c * 4 + 2]) << 32) | (static_cast<uint64_t>(pv[c * 4 + 3]) << 48));
         }
       }
     } else {

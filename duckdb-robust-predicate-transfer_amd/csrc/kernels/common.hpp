@@ -82,15 +82,7 @@ static_assert(kChunkRows % kSegRows == 0 && kTileRows % kChunkRows == 0, "chunks
 constexpr int kSliceThreads = 1024;                    // slice-probe workgroup (16 waves)
 constexpr int kLdsDirectMaxLog = 14;                   // filters <= 128 KiB: whole filter in LDS
 constexpr int kLdsProbeThreads = 1024;                 // whole-filter LDS probe workgroup (16 waves)
-#ifndef RPT_PARTITION_SMALL_P
-#define RPT_PARTITION_SMALL_P 1                        // partition of <= 4-slice filters: wave-aggregated counters
-#endif
-#ifndef RPT_VALU_INTERLEAVE
-#define RPT_VALU_INTERLEAVE 1                          // store_segment_bits: bit interleave on VALU (lanes 0-7)
-#endif
-#ifndef RPT_SEL_BALLOT_EXPAND
-#define RPT_SEL_BALLOT_EXPAND 1                        // dense selection vectors written 64 rows at a time, contiguously
-#endif
+// Dense selection vectors are written 64 rows at a time, contiguously ...
 #ifndef RPT_SEL_BALLOT_MIN
 #define RPT_SEL_BALLOT_MIN 192                         // ... from this many survivors per 512 rows (unpermute_sel)
 #endif
@@ -147,9 +139,6 @@ __device__ __forceinline__ bool valid_at(const uint64_t* validity, uint64_t idx)
 // MM over a full NULL-free segment of the batched loads (the bucketed level-1 scatter of a build): a
 // tournament over the lane's 8 values instead of a guarded min and max per value (VGPRs 111 -> 86): C5
 // build 7.58-7.65 -> 7.43-7.50 ms on one box (profiles/r04/ab_mm_tournament.txt).
-#ifndef RPT_MM_TOURNAMENT
-#define RPT_MM_TOURNAMENT 1
-#endif
 template <int K, bool DENSE, bool MM = false, bool NT = false, bool BATCH = false>
 __device__ __forceinline__ void load_hashes(const KeyArgs& a, uint64_t base, uint64_t n, uint32_t lane,
                                             uint64_t (&h)[8], bool (&ok)[8], int64_t* mm = nullptr) {
@@ -218,15 +207,9 @@ __device__ __forceinline__ void load_hashes(const KeyArgs& a, uint64_t base, uin
         if constexpr (K == kKeySplit) hv |= static_cast<uint64_t>((hi4[c] >> (8 * e)) & 0xFFu) << 32;
         if (Tr::kValues && !((vbits[c] >> e) & 1u)) hv = kNullHash;
         h[c * V + e] = hv;
-        if constexpr (MM && Tr::kValues && !RPT_MM_TOURNAMENT) {
-          if (off + e < rem && ((vbits[c] >> e) & 1u)) {
-            mm[0] = min(mm[0], static_cast<int64_t>(v[c * V + e]));
-            mm[1] = max(mm[1], static_cast<int64_t>(v[c * V + e]));
-          }
-        }
       }
     }
-    if constexpr (MM && Tr::kValues && RPT_MM_TOURNAMENT) {
+    if constexpr (MM && Tr::kValues) {
       if (rem == static_cast<uint32_t>(kSegRows) && vb == nullptr) {
         // a full segment without NULLs (uniform): the 8 values' min and max by a tournament (one compare
         // per pair yields both, then 3 + 3), instead of a guarded min and max per value
@@ -340,10 +323,6 @@ __device__ __forceinline__ uint32_t seg_row(int j, uint32_t lane) {
   }
 }
 
-// Wave-wide (min, max) of per-lane values, returned wave-uniform (scalar registers).
-#ifndef RPT_DPP_MINMAX
-#define RPT_DPP_MINMAX 1
-#endif
 // One DPP step on both 32-bit halves of an int64; lanes the row mask disables keep their own value.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int64_t dpp_i64(int64_t v) {
@@ -358,8 +337,8 @@ __device__ __forceinline__ void minmax_step(int64_t& mn, int64_t& mx) {
   mn = min(mn, dpp_i64<CTRL, ROW_MASK>(mn));
   mx = max(mx, dpp_i64<CTRL, ROW_MASK>(mx));
 }
+// Wave-wide (min, max) of per-lane values, returned wave-uniform (scalar registers).
 __device__ __forceinline__ void wave_minmax(int64_t& mn, int64_t& mx) {
-#if RPT_DPP_MINMAX
   // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: every lane holds its row's value;
   // row_bcast:15 (rows 1, 3) and row_bcast:31 (rows 2, 3): lane 63 holds the wave's. All VALU (DPP),
   // where __shfl_xor costs 24 ds_bpermute per call (the level-1 count: +0.28 ms per 1e9 build keys).
@@ -377,21 +356,6 @@ __device__ __forceinline__ void wave_minmax(int64_t& mn, int64_t& mx) {
   };
   mn = lane63(mn);
   mx = lane63(mx);
-#else
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    mn = min(mn, static_cast<int64_t>(__shfl_xor(static_cast<long long>(mn), d, 64)));
-    mx = max(mx, static_cast<int64_t>(__shfl_xor(static_cast<long long>(mx), d, 64)));
-  }
-  auto uniform = [](int64_t v) {
-    const uint64_t u = static_cast<uint64_t>(v);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(u));
-    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(u >> 32));
-    return static_cast<int64_t>((static_cast<uint64_t>(hi) << 32) | lo);
-  };
-  mn = uniform(mn);
-  mx = uniform(mx);
-#endif
 }
 // Fold a wave's uniform (min, max) into stats[0..1] (int64, device). A wave whose values cannot lower
 // the min or raise the max — the common case once a few waves have reported — skips the atomics.
@@ -404,38 +368,15 @@ __device__ __forceinline__ void publish_minmax(int64_t mn, int64_t mx, int64_t* 
   }
 }
 constexpr int64_t kMinInit = INT64_MAX, kMaxInit = INT64_MIN;  // "no value yet"
-// RPT_PROBE_BUFSTORE = 1 (measured, off): a few lanes' stores (a segment's 8 result words from lanes 0-7, its count
-// from lane 0) as buffer stores through a descriptor covering only those bytes, so the other lanes' stores are
-// dropped by the descriptor's range check instead of being skipped by a branch. A store behind an exec-skip branch
-// leaves the compiler's count of outstanding memory operations unknown at the pipelined probe loop's head, where it
-// then waits for all of them (s_waitcnt vmcnt(0)). Removing that wait did not speed the probe (JOBDIM int64 probe
-// 1.567-1.570 vs 1.577-1.579 ms, int32 and the gather probe unchanged, profiles/r06/ab_pipeline.txt): its skeleton
-// is bound by the result words' HBM writes inside the key stream (tools/ubench/ubench_skeleton.hip). Global memory
-// only (not LDS).
-#ifndef RPT_PROBE_BUFSTORE
-#define RPT_PROBE_BUFSTORE 0
-#endif
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-constexpr int kRawBufferWord3 = 0x00020000;  // gfx9 raw buffer descriptor word 3: 32-bit data format, no swizzle
-__device__ __forceinline__ void store_lanes_b64(uint64_t* base, uint32_t valid_bytes, uint32_t lane, uint64_t v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, static_cast<int>(valid_bytes), kRawBufferWord3);
-  __builtin_amdgcn_raw_buffer_store_b64(u32x2{static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32)}, r,
-                                        static_cast<int>(lane * 8), 0, 0);
-}
-__device__ __forceinline__ void store_lanes_b32(uint32_t* base, uint32_t valid_bytes, uint32_t lane, uint32_t v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, static_cast<int>(valid_bytes), kRawBufferWord3);
-  __builtin_amdgcn_raw_buffer_store_b32(v, r, static_cast<int>(lane * 4), 0, 0);
-}
 
 // The 8 pass flags a lane holds for a 512-row segment, in load_hashes<K, DENSE> order -> the segment's
-// row-ordered result words (8 x 64 bits, Arrow Find layout) and its survivor count. BUF: global outputs, written by
-// buffer stores (store_lanes_*); seg_counts may then be null (its store covers no bytes).
-template <int K, bool DENSE, bool BUF = false>
+// row-ordered result words (8 x 64 bits, Arrow Find layout) and its survivor count.
+template <int K, bool DENSE>
 __device__ __forceinline__ void store_segment_bits(const bool (&pass)[8], uint32_t lane, uint64_t seg,
                                                    uint64_t* __restrict__ out_bits, uint32_t* __restrict__ seg_counts) {
-  uint64_t word[8];
+  uint64_t mine = 0;
   uint32_t cnt = 0;
-  if constexpr (DENSE && RPT_VALU_INTERLEAVE) {
+  if constexpr (DENSE) {
     // lane w < 8 builds result word w from the two (V = 2) or four (V = 4) ballots it interleaves: the
     // bit spreading runs once on the vector unit instead of eight times on the scalar unit
     constexpr int V = KeyTraits<K>::kVec;
@@ -446,7 +387,6 @@ __device__ __forceinline__ void store_segment_bits(const bool (&pass)[8], uint32
       cnt += __popcll(b[j]);
     }
     const uint32_t w = lane & 7, c = w / V, q = w % V;
-    uint64_t mine = 0;
 #pragma unroll
     for (int e = 0; e < V; e++) {
       uint64_t src = 0;  // ballot c * V + e of this lane's word
@@ -455,46 +395,17 @@ __device__ __forceinline__ void store_segment_bits(const bool (&pass)[8], uint32
       if constexpr (V == 2) mine |= spread2(src >> (32 * q)) << e;
       else mine |= spread4(src >> (16 * q)) << e;
     }
-    if constexpr (BUF) {
-      store_lanes_b64(out_bits + seg * kWordsPerSeg, kWordsPerSeg * 8, lane, mine);
-      store_lanes_b32(seg_counts + seg, seg_counts != nullptr ? 4u : 0u, lane, cnt);
-    } else {
-      if (lane < kWordsPerSeg) out_bits[seg * kWordsPerSeg + lane] = mine;
-      if (seg_counts != nullptr && lane == 0) seg_counts[seg] = cnt;
-    }
-    return;
-  } else if constexpr (DENSE) {
-    constexpr int V = KeyTraits<K>::kVec;
-    uint64_t b[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      b[j] = ballot64(pass[j]);
-      cnt += __popcll(b[j]);
-    }
-#pragma unroll
-    for (int c = 0; c < 8 / V; c++) {
-#pragma unroll
-      for (int q = 0; q < V; q++) {
-        uint64_t x = 0;
-        if constexpr (V == 2) {
-          x = spread2(b[c * 2 + 0] >> (32 * q)) | (spread2(b[c * 2 + 1] >> (32 * q)) << 1);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; e++) x |= spread4(b[c * 4 + e] >> (16 * q)) << e;
-        }
-        word[c * V + q] = x;
-      }
-    }
   } else {
+    // general mapping: ballot j is result word j
+    uint64_t word[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       word[j] = ballot64(pass[j]);
       cnt += __popcll(word[j]);
     }
-  }
-  uint64_t mine = 0;
 #pragma unroll
-  for (int j = 0; j < 8; j++) mine = (lane == static_cast<uint32_t>(j)) ? word[j] : mine;
+    for (int j = 0; j < 8; j++) mine = (lane == static_cast<uint32_t>(j)) ? word[j] : mine;
+  }
   if (lane < kWordsPerSeg) out_bits[seg * kWordsPerSeg + lane] = mine;
   if (seg_counts != nullptr && lane == 0) seg_counts[seg] = cnt;
 }

@@ -75,17 +75,7 @@ __device__ __forceinline__ void part_store(T* p, T v) {
 // per-segment bijection works, so lane-major slots (j * 64 + lane: consecutive words across the wave,
 // no bank conflicts) instead of the row's own position (stride V words across lanes: 2- / 4-way
 // conflicts for int64 / int32 keys).
-#ifndef RPT_PARK_LANE_MAJOR
-#define RPT_PARK_LANE_MAJOR 1
-#endif
-template <int K, bool DENSE>
-__device__ __forceinline__ uint32_t park_slot(int j, uint32_t lane) {
-#if RPT_PARK_LANE_MAJOR
-  return static_cast<uint32_t>(j) * 64u + lane;
-#else
-  return seg_row<K, DENSE>(j, lane);
-#endif
-}
+__device__ __forceinline__ uint32_t park_slot(int j, uint32_t lane) { return static_cast<uint32_t>(j) * 64u + lane; }
 
 // ---- partitioned probe, A: bucket a tile of kTileRows rows by filter slice ------------------------
 // Row r of the tile gets record slice_record(hash) stored at position pos(r) of the tile's
@@ -115,9 +105,6 @@ __host__ __device__ constexpr uint64_t partition_lds_bytes(uint32_t n_slices, ui
 // (DESIGN §5): 1.84 -> 1.79 ms per 1e9 rows (profiles/r04/ab_part_nopark.txt). TM = 2 (one workgroup per CU,
 // 128 VGPRs): 32 VGPRs, 115 used: C3 int32 partition 2.37 -> 2.26-2.28 ms, int64 2.64 -> 2.60-2.64, builds
 // -5 % (profiles/r04/ab_part_nopark_tm2.txt).
-#ifndef RPT_PART_NOPARK
-#define RPT_PART_NOPARK 1
-#endif
 template <int K, bool DENSE, bool MM, int TM, int SP = 0>
 __global__ __launch_bounds__(kTileThreads, TM == 1 ? RPT_PARTITION_MIN_WAVES : 4) void partition_kernel(
     KeyArgs a, uint64_t n, uint32_t slice_mask, uint64_t n_tiles, uint32_t* __restrict__ recs,
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(kTileThreads, TM == 1 ? RPT_PARTITION_MIN_WAVES : 4
   constexpr bool PAD = TM == 1;
   constexpr uint64_t kTR = kTileRows * TM;               // rows of this tile
   constexpr int kRPT = static_cast<int>(kTR / kTileThreads), kSPW = kRPT / 8;
-  constexpr bool NOPARK = RPT_PART_NOPARK && ((K == 1 && TM == 1) || TM == 2) && SP == 0 && DENSE;  // records stay in registers
+  constexpr bool NOPARK = ((K == 1 && TM == 1) || TM == 2) && SP == 0 && DENSE;  // records stay in registers
   extern __shared__ uint32_t s_dyn[];
   const uint32_t n_slices = slice_mask + 1;
   const uint64_t tile_cap = tile_cap_for(n_slices, TM);
@@ -176,7 +163,7 @@ __global__ __launch_bounds__(kTileThreads, TM == 1 ? RPT_PARTITION_MIN_WAVES : 4
       for (int j = 0; j < 8; j++) {
         const uint32_t sl = static_cast<uint32_t>(hh[j] >> (kLogNumMasks + 6 + kSliceLog)) & slice_mask;
         if constexpr (NOPARK) rec[sg * 8 + j] = slice_record(hh[j]);
-        else s_rec[seg_local + park_slot<K, DENSE>(j, lane)] = slice_record(hh[j]);
+        else s_rec[seg_local + park_slot(j, lane)] = slice_record(hh[j]);
         sl2[(sg * 8 + j) >> 1] |= sl << (16 * (j & 1));
         if constexpr (SP > 0) {
 #pragma unroll
@@ -238,7 +225,7 @@ __global__ __launch_bounds__(kTileThreads, TM == 1 ? RPT_PARTITION_MIN_WAVES : 4
     for (int sg = 0; sg < (NOPARK ? 0 : kSPW); sg++) {
       const uint32_t seg_local = wave * (kSPW * kSegRows) + sg * kSegRows;
 #pragma unroll
-      for (int j = 0; j < 8; j++) rec[sg * 8 + j] = s_rec[seg_local + park_slot<K, DENSE>(j, lane)];
+      for (int j = 0; j < 8; j++) rec[sg * 8 + j] = s_rec[seg_local + park_slot(j, lane)];
     }
     __syncthreads();
     [[maybe_unused]] uint32_t cur[SP > 0 ? SP : 1];
@@ -402,18 +389,14 @@ __device__ __forceinline__ SliceWork slice_work(uint32_t item, uint32_t splits, 
   return SliceWork{slice, row, lo + cnt * part / splits, lo + cnt * (part + 1) / splits};
 }
 
-// Work items are dealt to workgroups round-robin, and workgroup b runs on XCD b % 8. With
-// RPT_SLICE_XCD_MAP the items are renumbered so that each XCD gets a contiguous range of
-// (slice, split) items. The workgroups resident on one XCD then probe adjacent slices over the same
-// tiles at about the same time. Adjacent slices' runs are adjacent in each tile, so a run's partial
+// Work items are dealt to workgroups round-robin, and workgroup b runs on XCD b % 8. The items
+// are renumbered so that each XCD gets a contiguous range of (slice, split) items. The workgroups
+// resident on one XCD then probe adjacent slices over the same tiles at about the same time. Adjacent slices' runs are adjacent in each tile, so a run's partial
 // first and last 128-B lines, fetched by its neighbour's workgroup, can be L2 hits instead of
 // over-fetch. Needs item and grid counts divisible by the XCD count (otherwise: identity).
-#ifndef RPT_SLICE_XCD_MAP
-#define RPT_SLICE_XCD_MAP 1
-#endif
 constexpr uint32_t kXcds = 8;
 __device__ __forceinline__ uint32_t xcd_item(uint32_t item, uint32_t n_items) {
-  if (!RPT_SLICE_XCD_MAP || n_items % kXcds != 0 || gridDim.x % kXcds != 0) return item;
+  if (n_items % kXcds != 0 || gridDim.x % kXcds != 0) return item;
   return (item % kXcds) * (n_items / kXcds) + item / kXcds;
 }
 
@@ -622,9 +605,6 @@ __global__ __launch_bounds__(kSliceThreads) void slice_probe_kernel(const uint64
 #ifndef RPT_EXP_STORE_SKIP_ZERO
 #define RPT_EXP_STORE_SKIP_ZERO 0
 #endif
-#ifndef RPT_SLICE_INSERT_DEDUP
-#define RPT_SLICE_INSERT_DEDUP 1  // drop a record equal to its slot's previous one (below)
-#endif
 constexpr int kSliceMergeAtomic = 0, kSliceMergeStore = 1, kSliceMergeAdaptive = 2, kSliceMergeStoreAll = 3;
 __global__ __launch_bounds__(kSliceThreads) void slice_insert_kernel(uint64_t* __restrict__ words, uint32_t splits,
                                                                     uint64_t n_tiles,
@@ -722,7 +702,7 @@ __global__ __launch_bounds__(kSliceThreads) void slice_insert_kernel(uint64_t* _
         // word serialize (one key repeated 4 Mi times: 3.7 ms, profiles/r05/insert_duplicates.jsonl)
 #pragma unroll
         for (uint32_t e = 0; e < kRunPad; e++) {
-          if (e < nreal[u] && (!RPT_SLICE_INSERT_DEDUP || e == 0 || rec[u][e >> 2][e & 3] != rec[u][(e - 1) >> 2][(e - 1) & 3])) {
+          if (e < nreal[u] && (e == 0 || rec[u][e >> 2][e & 3] != rec[u][(e - 1) >> 2][(e - 1) & 3])) {
             const uint32_t rec1 = rec[u][e >> 2][e & 3];
             atomicOr(reinterpret_cast<unsigned long long*>(&s_slice[rec_word(rec1)]),
                      static_cast<unsigned long long>(rec_mask(s_rmasks, rec1)));
@@ -918,7 +898,6 @@ __global__ __launch_bounds__(kUnpermuteSelThreads<TM>) void unpermute_sel_kernel
   __syncthreads();
   uint32_t woff = block_offs[tile / kTileBlock] + tile_pre[tile];
   for (uint32_t w = 0; w < wave; w++) woff += s_wtot[w];
-#if RPT_SEL_BALLOT_EXPAND
   // Dense segments (>= RPT_SEL_BALLOT_MIN survivors of 512): row-ordered 64-row words (lane 8k + j holds
   // byte j of word k; the bytes are ORed within each group of 8 lanes by DPP), expanded word by word
   // so each store writes one contiguous run of survivors. Sparse segments: each lane writes its own
@@ -952,17 +931,5 @@ __global__ __launch_bounds__(kUnpermuteSelThreads<TM>) void unpermute_sel_kernel
 #pragma unroll
     for (int k = 0; k < 8; k++) o += expand_word_sel(readlane64(v, 8 * k), row0 + 64 * k, lane, row_sel, out_sel + o);
   }
-#else
-#pragma unroll
-  for (uint32_t sg = 0; sg < kSegsPerWave; sg++) {
-    uint32_t b = bytes[sg], o = woff + excl[sg];
-    const uint32_t row0 = static_cast<uint32_t>((seg0 + sg) * kSegRows) + lane * 8;
-    while (b) {
-      const uint32_t row = row0 + static_cast<uint32_t>(__builtin_ctz(b));
-      out_sel[o++] = row_sel ? row_sel[row] : row;
-      b &= b - 1;
-    }
-  }
-#endif
 }
 }  // namespace rpt

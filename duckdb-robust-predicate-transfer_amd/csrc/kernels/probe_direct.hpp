@@ -22,16 +22,9 @@ namespace rpt {
 #ifndef RPT_LDS_I64_GROUP
 #define RPT_LDS_I64_GROUP 1  // segments per group in the int64 whole-filter LDS probe (r02: 2 and 3 were slower)
 #endif
-#ifndef RPT_PROBE_SCHED_BARRIER
-#define RPT_PROBE_SCHED_BARRIER 0  // 1: scheduling barrier after the prefetch loads (measured: no gain, see the loop)
-#endif
 #ifndef RPT_HYBRID_I64_GROUP
 #define RPT_HYBRID_I64_GROUP 2  // segments per group in the int64 hybrid LDS/L2 probe (1 / 2 / 3: 2.82 / 2.59 / 2.87 ms
                                 // per 1e9 keys, profiles/r06/ab_hybrid_group.txt; int32 takes RPT_PROBE_PREFETCH = 2)
-#endif
-#ifndef RPT_PROBE_RING
-#define RPT_PROBE_RING 2  // register buffers of prefetched groups: 2 = ping-pong (group g + 1 in flight while g is
-                          // probed), 3 = groups g + 1 and g + 2 in flight
 #endif
 template <int K> struct RawSeg {
   static constexpr int V = KeyTraits<K>::kVec;
@@ -77,18 +70,14 @@ __device__ __forceinline__ void probe8(const uint64_t* __restrict__ words, const
   for (int j = 0; j < 8; j++) pass[j] = ok[j] && (w[j] & m[j]) == m[j];
 }
 
-// zero[0 .. n_zero): words the selection-vector tail's look-back needs cleared (compact_lookback_kernel's group
-// states and ticket), cleared here so the tail needs no launch of its own; nullptr when there is no such tail.
 // The body of probe_bits_kernel (HYBRID = false) and probe_bits_hybrid_kernel (HYBRID = true: filters of 256 KiB,
 // the first 128 KiB staged in LDS, the rest gathered from L2).
 template <int K, bool DENSE, bool FILTER_IN_LDS, int THREADS, bool HYBRID>
 __device__ __forceinline__ void probe_bits_body(const uint64_t* __restrict__ words, uint64_t block_mask, KeyArgs a,
                                                 uint64_t n, uint64_t n_segs, uint64_t* __restrict__ out_bits,
-                                                uint32_t* __restrict__ seg_counts, uint64_t* __restrict__ zero,
-                                                uint32_t n_zero) {
+                                                uint32_t* __restrict__ seg_counts) {
   __shared__ uint64_t s_masks[kNumMasks];
   extern __shared__ uint64_t s_filter[];
-  for (uint32_t i = blockIdx.x * THREADS + threadIdx.x; i < n_zero; i += gridDim.x * THREADS) zero[i] = 0;
   fill_mask_table(s_masks);
   if constexpr (FILTER_IN_LDS) {
     const uint64_t staged = HYBRID ? kHybridWords - 1 : block_mask;
@@ -111,10 +100,9 @@ __device__ __forceinline__ void probe_bits_body(const uint64_t* __restrict__ wor
       // 1.05 / 1.06; 256 KiB gather 4.48 / 4.33 / 4.30
       constexpr int S = (FILTER_IN_LDS && KeyTraits<K>::kVec == 2) ? (HYBRID ? RPT_HYBRID_I64_GROUP : RPT_LDS_I64_GROUP)
                                                                    : RPT_PROBE_PREFETCH;
-      constexpr int NB = RPT_PROBE_RING;
       const bool ok[8] = {true, true, true, true, true, true, true, true};
       const uint64_t first = seg;
-      RawSeg<K> R[NB][S];
+      RawSeg<K> R[2][S];  // ping-pong: group g + 1 is in flight while g is probed
       auto load_group = [&](RawSeg<K>(&R)[S], uint64_t g) {
 #pragma unroll
         for (int q = 0; q < S; q++) {
@@ -143,28 +131,21 @@ __device__ __forceinline__ void probe_bits_body(const uint64_t* __restrict__ wor
             R[q].hashes(h);
             probe8<FILTER_IN_LDS, HYBRID>(words, s_filter, s_masks, block_mask, h, ok, pass);
 #endif
-            store_segment_bits<K, DENSE, RPT_PROBE_BUFSTORE>(pass, lane, sg, out_bits, seg_counts);
+            store_segment_bits<K, DENSE>(pass, lane, sg, out_bits, seg_counts);
           }
         }
       };
       const uint64_t step = S * total_waves;
-#pragma unroll
-      for (int b = 0; b < NB - 1; b++) load_group(R[b], seg + b * step);
+      load_group(R[0], seg);
       bool more = true;
       while (more) {
-        // buffer b holds group seg; before probing it, the group NB - 1 steps ahead goes into the buffer the
+        // buffer b holds group seg; before probing it, the next group goes into the other buffer, which the
         // previous iteration freed (compile-time indices: the loop over b is unrolled)
 #pragma unroll
-        for (int b = 0; b < NB; b++) {
+        for (int b = 0; b < 2; b++) {
           if (more) {
-            load_group(R[(b + NB - 1) % NB], seg + (NB - 1) * step);
+            load_group(R[b ^ 1], seg + step);
             asm volatile("" ::: "memory");  // issue the next group's loads before this one's work
-#if RPT_PROBE_SCHED_BARRIER
-            // ... and keep the scheduler from hoisting this group's hashing above them: it does in the second half of
-            // the unrolled int64 ping-pong, whose wait for its data then finds no loads in flight. Pinning the order
-            // measured no faster (profiles/r06/ab_pipeline.txt): 16 waves per CU hide that wait.
-            __builtin_amdgcn_sched_barrier(0);
-#endif
             probe_group(R[b], seg);
             seg += step;
             more = seg < n_full;
@@ -189,19 +170,15 @@ template <int K, bool DENSE, bool FILTER_IN_LDS, int THREADS = kBlockThreads>
 __global__ __launch_bounds__(THREADS) void probe_bits_kernel(const uint64_t* __restrict__ words,
                                                                   uint64_t block_mask, KeyArgs a, uint64_t n,
                                                                   uint64_t n_segs, uint64_t* __restrict__ out_bits,
-                                                                  uint32_t* __restrict__ seg_counts,
-                                                                  uint64_t* __restrict__ zero, uint32_t n_zero) {
-  probe_bits_body<K, DENSE, FILTER_IN_LDS, THREADS, false>(words, block_mask, a, n, n_segs, out_bits, seg_counts, zero,
-                                                           n_zero);
+                                                                  uint32_t* __restrict__ seg_counts) {
+  probe_bits_body<K, DENSE, FILTER_IN_LDS, THREADS, false>(words, block_mask, a, n, n_segs, out_bits, seg_counts);
 }
 template <int K, bool DENSE>
 __global__ __launch_bounds__(kLdsProbeThreads) void probe_bits_hybrid_kernel(const uint64_t* __restrict__ words,
                                                                              uint64_t block_mask, KeyArgs a, uint64_t n,
                                                                              uint64_t n_segs, uint64_t* __restrict__ out_bits,
-                                                                             uint32_t* __restrict__ seg_counts,
-                                                                             uint64_t* __restrict__ zero, uint32_t n_zero) {
-  probe_bits_body<K, DENSE, true, kLdsProbeThreads, true>(words, block_mask, a, n, n_segs, out_bits, seg_counts, zero,
-                                                          n_zero);
+                                                                             uint32_t* __restrict__ seg_counts) {
+  probe_bits_body<K, DENSE, true, kLdsProbeThreads, true>(words, block_mask, a, n, n_segs, out_bits, seg_counts);
 }
 
 // ---- small batches: probe + compaction in ONE workgroup ----------------------------------------

@@ -54,20 +54,6 @@
 #include "kernels/insert_masked.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
-#ifndef RPT_FUSED_SEL
-#define RPT_FUSED_SEL 1  // rpt_bf_probe, PARTITIONED: the unpermute writes the selection vector itself
-#endif
-#ifndef RPT_L1_FIXED_PCT
-// Fixed chunks per list, in % of an even split's (+ 1). Measured (C5 probe ms, same box): 0 -> 8.70-8.75,
-// 110 / 125 -> 8.82-8.85: fixed ids spare the scatter its extent atomics and waits (3.15 -> 3.06 ms), but
-// the larger workspace (+6 GB at 1e9 rows: the overflow pool stays sized for the worst case) costs the
-// slice probe, partition and unpermute more (slice probe 2.32 -> 2.48 ms).
-#define RPT_L1_FIXED_PCT 0
-#endif
-
-#ifndef RPT_LOOKBACK_TAIL
-#define RPT_LOOKBACK_TAIL 0  // 1: the direct strategies' sel tail in one look-back launch (measured slower, DESIGN §5 rejected list)
-#endif
 #ifndef RPT_LDS_HYBRID_MAX_LOG
 #define RPT_LDS_HYBRID_MAX_LOG 17  // the LDS strategy up to 2^this blocks; above 2^14 the first 128 KiB in LDS, the rest
                                    // gathered from L2 (probe_direct.hpp). ms per 1e9 keys against AUTO's previous pick
@@ -77,28 +63,25 @@
                                    // 16 Mi rows: 107 vs 112 us int64, 99 vs 106 us int32; profiles/r06/ab_hybrid2.txt,
                                    // ab_hybrid_1m.txt, first pass ab_hybrid.txt)
 #endif
-#ifndef RPT_SUMSCAN_TAIL
-#define RPT_SUMSCAN_TAIL 0  // 1: the direct strategies' group sums and their scan in one launch (measured: no gain)
+// Work items of a slice skewed probe keys overload: RPT_SLICE_SKEW_MULT x finer (1: off; rpt::SkewItems)
+#ifndef RPT_SLICE_SKEW_MULT
+#define RPT_SLICE_SKEW_MULT 32
 #endif
 
-// The product build runs the tuning macros at the defaults the GPU suite tests. Other values exist for
-// A/B timing only (tools/build_variants.sh builds them under other names, without RPT_PRODUCT_BUILD);
-// several were never run through the parity suite (tuning macros).
+// The product build runs every tuning macro of csrc/ at the default the GPU suite tests
+// (tests/test_build_guards.py checks that none is missing here). Other values exist for A/B timing only
+// (tools/build_variants.sh builds them under other names, without RPT_PRODUCT_BUILD); several were never
+// run through the parity suite (tuning macros).
 #if defined(RPT_PRODUCT_BUILD)
 static_assert(RPT_SLICE_LOG == 14 && RPT_RUN_ALIGN == 8 && RPT_BUCKET_SLICE_LOG == 8 && RPT_L1_TILE_ROWS == 16384 &&
-                  RPT_L1_FIXED_PCT == 0 && RPT_BUCKET_UNPERMUTE_THREADS == 256 && RPT_SLICE_UNROLL == 4 &&
-                  RPT_PARTITION_MIN_WAVES == 8 && RPT_PROBE_PREFETCH == 2 && RPT_SEL_BALLOT_MIN == 192 &&
-                  RPT_COMPACT_BALLOT_MIN == 384 && RPT_COMPACT_STAGE == 3072 && RPT_LDS_I64_GROUP == 1 &&
-                  RPT_PROBE_RING == 2 && RPT_LOOKBACK_TAIL == 0 && RPT_COMPACT_V16 == 0 && RPT_SUMSCAN_TAIL == 0 &&
-                  RPT_PROBE_BUFSTORE == 0 && RPT_PROBE_SCHED_BARRIER == 0 && RPT_LDS_HYBRID_MAX_LOG == 17 &&
-                  RPT_HYBRID_I64_GROUP == 2,
+                  RPT_BUCKET_UNPERMUTE_THREADS == 256 && RPT_SLICE_UNROLL == 4 && RPT_PARTITION_MIN_WAVES == 8 &&
+                  RPT_PROBE_PREFETCH == 2 && RPT_SEL_BALLOT_MIN == 192 && RPT_COMPACT_BALLOT_MIN == 384 &&
+                  RPT_COMPACT_STAGE == 3072 && RPT_LDS_I64_GROUP == 1 && RPT_LDS_HYBRID_MAX_LOG == 17 &&
+                  RPT_HYBRID_I64_GROUP == 2 && RPT_SLICE_SKEW_MULT == 32,
               "product build: tuning macros must keep their tested defaults (use tools/build_variants.sh)");
-static_assert(RPT_FUSED_SEL == 1 && RPT_NT_KEY_LOADS == 1 && RPT_NT_PART_STORES == 1 && RPT_NT_PROBE_LOADS == 1 &&
-                  RPT_NT_REC_LOADS == 0 && RPT_NT_SLICE_LOADS == 1 && RPT_PARK_LANE_MAJOR == 1 && RPT_SLICE_XCD_MAP == 1 &&
-                  RPT_PARTITION_SMALL_P == 1 && RPT_VALU_INTERLEAVE == 1 && RPT_SEL_BALLOT_EXPAND == 1 &&
-                  RPT_DPP_MINMAX == 1 && RPT_DPP_SCAN == 1 && RPT_PART_NOPARK == 1 && RPT_SCATTER_POS_PACK == 2 &&
-                  RPT_MM_TOURNAMENT == 1,
-              "product build: tuning switches must keep their tested defaults (use tools/build_variants.sh)");
+static_assert(RPT_NT_KEY_LOADS == 1 && RPT_NT_PART_STORES == 1 && RPT_NT_PROBE_LOADS == 1 && RPT_NT_REC_LOADS == 0 &&
+                  RPT_NT_SLICE_LOADS == 1,
+              "product build: load/store hints must keep their tested defaults (use tools/build_variants.sh)");
 #endif
 
 // =================================================================================================
@@ -446,8 +429,6 @@ struct ProbeWorkspace {
   uint16_t* pos1;          // row -> position in its level-1 tile's bucket-sorted order
   uint64_t* bits2;         // level-2 result bits (w-space order)
   uint32_t* heavy;         // partitioned: [slice] epoch stamp of a slice skewed probe keys overload (rpt::SkewItems)
-  uint64_t* lb_state;      // gather / LDS: [group] look-back states + [n_groups] ticket (compact_lookback_kernel),
-                           // or group_sum_scan_kernel's flagged group sums (u32); cleared by the probe kernel
 };
 
 uint32_t slice_count(int log_num_blocks) {
@@ -459,15 +440,6 @@ uint32_t bucket_count(int log_num_blocks) {
   return 1u << std::max(0, log_num_blocks - rpt::kSliceLog - rpt::kBucketSliceLog);
 }
 
-// (slice, split) work items of the slice probe: RPT_SLICE_SPLIT_MULT x one resident round (the grid stays one round
-// and walks them)
-#ifndef RPT_SLICE_SPLIT_MULT
-#define RPT_SLICE_SPLIT_MULT 1
-#endif
-// Work items of a slice skewed probe keys overload: RPT_SLICE_SKEW_MULT x finer (1: off; rpt::SkewItems)
-#ifndef RPT_SLICE_SKEW_MULT
-#define RPT_SLICE_SKEW_MULT 32
-#endif
 // Stamps of the eager skewed partitioned probes: 2, 3, ... (0 is what a captured probe's memset leaves, 1 the
 // stamp every captured probe uses, so an eager call's stamp is never a captured one's, wrap-around included).
 std::atomic<uint32_t> g_skew_epoch{1};
@@ -552,8 +524,7 @@ L1Geom l1_geom(uint64_t n, int log_num_blocks) {
   g.nb = bucket_count(log_num_blocks);
   g.groups = n >= min_rows ? rpt::kL1Groups : 1u;
   g.n_lists = static_cast<uint64_t>(g.groups) * g.nb;
-  const uint64_t even = ceil_div(ceil_div(n, g.n_lists), rpt::kChunkRows);  // chunks per list of an even split
-  g.k_fixed = ceil_div(even * RPT_L1_FIXED_PCT, 100) + 1;
+  g.k_fixed = 1;
   const uint64_t group_chunks = ceil_div(g.t1, g.groups) * (rpt::kL1TileRows / rpt::kChunkRows);  // rows of one group
   const uint64_t cmax = group_chunks + 1;  // chunks of one list
   g.n_ext = cmax > g.k_fixed ? ceil_div(cmax - g.k_fixed, rpt::kExtentChunks) : 0;
@@ -581,27 +552,15 @@ uint32_t tile_mult_of(uint32_t n_slices) {
 // Layout (all 256-aligned): bits | seg_counts | group_sums | group_offs, then for the partitioned
 // strategy recs | pos | passb | runs | runs_tm (whole 16 Ki-row tiles), and for the bucketed one the
 // same level-2 arrays over level2_tiles_max tiles of 256 slices plus the level-1 arrays.
-// RPT_LOOKBACK_TAIL = 1 runs the direct strategies' selection-vector tail as one look-back launch
-// (compact_lookback_kernel) instead of group sums + their scan + the compaction; measured slower, so off.
-bool lookback_tail(int strategy) {
-  return RPT_LOOKBACK_TAIL && (strategy == RPT_PROBE_GATHER || strategy == RPT_PROBE_LDS);
-}
-// RPT_SUMSCAN_TAIL: the direct strategies' group sums + scan as one launch whose highest-numbered workgroup scans
-// (flagged group sums the probe kernel clears), then the compaction: two dependent launches after the probe, not three.
-bool sumscan_tail(int strategy) {
-  return RPT_SUMSCAN_TAIL && !lookback_tail(strategy) && (strategy == RPT_PROBE_GATHER || strategy == RPT_PROBE_LDS);
-}
 
 size_t workspace_layout(uint64_t n, int log_num_blocks, int strategy, void* base, ProbeWorkspace* ws) {
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
   const uint64_t T = rpt::kTileRows;
-  constexpr int kParts = 22;
+  constexpr int kParts = 21;
   size_t sz[kParts] = {align256(n_segs * rpt::kWordsPerSeg * 8), align256(n_groups * rpt::kGroupSegs * 4),
                        align256(n_groups * 4), align256(n_groups * 4)};
   const bool part = strategy == RPT_PROBE_PARTITIONED, buck = strategy == RPT_PROBE_BUCKETED;
-  if (lookback_tail(strategy)) sz[21] = align256((n_groups + 1) * 8);
-  if (sumscan_tail(strategy)) sz[21] = align256(n_groups * 4);
   if (part || buck) {
     const uint32_t slices = part ? slice_count(log_num_blocks) : rpt::kBucketSlices;
     const uint32_t tm = part ? tile_mult_of(slices) : 1u;
@@ -656,7 +615,6 @@ size_t workspace_layout(uint64_t n, int log_num_blocks, int strategy, void* base
     ws->bits2 = static_cast<uint64_t*>(at(18));
     ws->hash_hi = static_cast<uint8_t*>(at(19));
     ws->heavy = static_cast<uint32_t*>(at(20));
-    ws->lb_state = static_cast<uint64_t*>(at(21));
   }
   return total;
 }
@@ -771,11 +729,10 @@ unsigned lds_probe_grid(int device, int log_num_blocks, uint64_t n_segs) {
 
 template <int K, bool D>
 void launch_probe_bits_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                         uint64_t n_segs, uint64_t* bits, uint32_t* counts, uint64_t* zero = nullptr,
-                         uint32_t n_zero = 0) {
+                         uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
   ProfScope prof(inst_name<K, D, false, rpt::kBlockThreads>("probe_bits_kernel"), s);
   hipLaunchKernelGGL((rpt::probe_bits_kernel<K, D, false>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts, zero, n_zero);
+                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts);
   prof.end();
 }
 
@@ -794,7 +751,7 @@ void launch_probe_small_t(hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a
 void allow_dynamic_lds(const void* fn);
 template <int K, bool D>
 void launch_probe_bits_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                             uint64_t n_segs, uint64_t* bits, uint32_t* counts, uint64_t* zero, uint32_t n_zero) {
+                             uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
   if (bf->log_num_blocks > rpt::kLdsDirectMaxLog) {  // hybrid: the first 128 KiB in LDS, the rest from L2
     const size_t lds = 8ULL << rpt::kLdsDirectMaxLog;
     static std::once_flag once_h;
@@ -804,7 +761,7 @@ void launch_probe_bits_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, con
     ProfScope prof(inst_name<K, D>("probe_bits_hybrid_kernel"), s);
     hipLaunchKernelGGL((rpt::probe_bits_hybrid_kernel<K, D>), dim3(grid),
                        dim3(rpt::kLdsProbeThreads), lds, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs,
-                       bits, counts, zero, n_zero);
+                       bits, counts);
     prof.end();
     return;
   }
@@ -813,7 +770,7 @@ void launch_probe_bits_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, con
   std::call_once(once, [] { allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_kernel<K, D, true, rpt::kLdsProbeThreads>)); });
   ProfScope prof(inst_name<K, D, true, rpt::kLdsProbeThreads>("probe_bits_kernel"), s);
   hipLaunchKernelGGL((rpt::probe_bits_kernel<K, D, true, rpt::kLdsProbeThreads>), dim3(grid), dim3(rpt::kLdsProbeThreads), lds,
-                     s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts, zero, n_zero);
+                     s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts);
   prof.end();
 }
 
@@ -867,7 +824,7 @@ void launch_partition_tm(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, ui
                          uint64_t n_tiles, uint32_t* recs, uint16_t* pos, uint32_t* runs, int64_t* stats,
                          const uint32_t* dev_n_tiles, const uint32_t* chunk_map) {
   if constexpr (TM == 1 && SP == 0) {
-    if (RPT_PARTITION_SMALL_P && slice_mask + 1 <= 4) {  // few slices: wave-aggregated slice counters
+    if (slice_mask + 1 <= 4) {  // few slices: wave-aggregated slice counters
       launch_partition_tm<K, D, MM, 1, 4>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, chunk_map);
       return;
     }
@@ -1587,21 +1544,13 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
   const bool dense = dense_ok(col, row_sel);
-  // the look-back tail's group states and ticket (compact_lookback_kernel) or the sum+scan tail's flagged group
-  // sums (group_sum_scan_kernel), cleared by the probe kernel (64-bit words)
-  const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
-  const uint32_t lb_words = !ws.lb_state ? 0u
-                            : lookback_tail(strategy) ? static_cast<uint32_t>(n_groups + 1)
-                                                      : static_cast<uint32_t>(ceil_div(n_groups, 2));
   if (strategy == RPT_PROBE_GATHER) {
     const unsigned grid = persistent_grid(bf->device, n_segs);
-    RPT_DISPATCH_KD(launch_probe_bits_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts,
-                    ws.lb_state, lb_words);
+    RPT_DISPATCH_KD(launch_probe_bits_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
     RPT_LAUNCHED("probe_bits_kernel");
   } else if (strategy == RPT_PROBE_LDS) {
     const unsigned grid = lds_probe_grid(bf->device, L, n_segs);
-    RPT_DISPATCH_KD(launch_probe_bits_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts,
-                    ws.lb_state, lb_words);
+    RPT_DISPATCH_KD(launch_probe_bits_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
     RPT_LAUNCHED("probe_bits_kernel<lds>");
   } else {
     // PARTITIONED: the key column, tiles of slice_count(L) slices. BUCKETED: level 1 first, then the
@@ -1663,7 +1612,7 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
     const uint64_t per_cu = std::max<uint64_t>(1, (160ULL << 10) / slice_lds);
     const uint64_t resident = static_cast<uint64_t>(cus) * per_cu;
     const uint32_t splits = static_cast<uint32_t>(
-        std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, RPT_SLICE_SPLIT_MULT * resident / grid_slices)));
+        std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, resident / grid_slices)));
     skew.base = grid_slices * splits;
     const uint32_t n_items = skew.base * (skewed ? 1 + skew.mult : 1);
     ProfScope prof6_("slice_probe_kernel", s);
@@ -1673,7 +1622,7 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
     prof6_.end();
     RPT_LAUNCHED("slice_probe_kernel");
     const uint64_t cap = rpt::tile_cap_for(tile_slices, tm);
-    if (RPT_FUSED_SEL && !buck && out_sel != nullptr && out_count_dev != nullptr) {
+    if (!buck && out_sel != nullptr && out_count_dev != nullptr) {
       // tile survivor counts (in seg_counts; then their prefix inside blocks of 256 tiles) -> block sums and
       // block offsets (in the unused result-bit area) -> sel
       uint32_t* tile_counts = ws.seg_counts;
@@ -1785,32 +1734,6 @@ int rpt_bf_probe_phase2(const rpt_bf* bf, const uint32_t* row_sel, uint64_t n, u
   ProbeWorkspace ws;
   workspace_layout(n, L, strategy, workspace, &ws);
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
-  const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
-  if (lookback_tail(strategy)) {
-    // one launch: group offsets by look-back (phase 1's probe kernel cleared the states and the ticket)
-    ProfScope prof10_("compact_lookback_kernel", s);
-    hipLaunchKernelGGL(rpt::compact_lookback_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
-                       ws.bits, ws.seg_counts, n_segs, static_cast<uint32_t>(n_groups), ws.lb_state, row_sel, out_sel,
-                       out_count_dev);
-    prof10_.end();
-    RPT_LAUNCHED("compact_lookback_kernel");
-    return RPT_OK;
-  }
-  if (sumscan_tail(strategy)) {
-    // group sums + scan in one launch (phase 1's probe kernel cleared the done counter), then the compaction
-    ProfScope prof8_("group_sum_scan_kernel", s);
-    hipLaunchKernelGGL(rpt::group_sum_scan_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
-                       ws.seg_counts, n_segs, static_cast<uint32_t>(n_groups), reinterpret_cast<uint32_t*>(ws.lb_state),
-                       ws.group_offs, out_count_dev);
-    prof8_.end();
-    RPT_LAUNCHED("group_sum_scan_kernel");
-    ProfScope prof10_("compact_kernel", s);
-    hipLaunchKernelGGL(rpt::compact_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
-                       ws.bits, ws.seg_counts, n_segs, ws.group_offs, row_sel, out_sel);
-    prof10_.end();
-    RPT_LAUNCHED("compact_kernel");
-    return RPT_OK;
-  }
   return launch_sel_tail(s, ws.bits, ws.seg_counts, ws.group_sums, ws.group_offs, n_segs, row_sel, out_sel, out_count_dev);
 }
 

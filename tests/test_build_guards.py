@@ -41,12 +41,32 @@ def syntax_check(*defines):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-@pytest.mark.parametrize("macro", ["RPT_SLICE_UNROLL=2", "RPT_L1_TILE_ROWS=8192", "RPT_NT_REC_LOADS=1"])
+@pytest.mark.parametrize("macro", ["RPT_SLICE_UNROLL=2", "RPT_L1_TILE_ROWS=8192", "RPT_NT_REC_LOADS=1",
+                                   "RPT_SLICE_SKEW_MULT=1"])
 def test_product_build_pins_tuning_macros(macro):
     """Tuning macros other than the defaults the GPU suite runs are for A/B variants only."""
     r = syntax_check("RPT_PRODUCT_BUILD=1", macro)
     assert r.returncode != 0 and "must keep their tested defaults" in r.stderr
     assert syntax_check(macro).returncode == 0
+
+
+def test_product_build_pins_every_tuning_macro():
+    """Every macro csrc/ lets the command line override (#ifndef RPT_X / #define RPT_X) is named in a product
+    static_assert of rpt_gpu.hip, so no HIPFLAGS override changes a product kernel unnoticed. Include guards and
+    the RPT_EXP_* measurement macros (refused outright, above) are not tuning macros."""
+    import glob
+    import re
+
+    overridable = set()
+    for path in glob.glob(os.path.join(PKG, "csrc", "**", "*.*"), recursive=True):  # .hip, .hpp, .h, .cpp
+        text = open(path).read()
+        overridable.update(re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(RPT_\w+)[ \t]*\n[ \t]*#[ \t]*define[ \t]+\1\b", text, re.M))
+    overridable = {m for m in overridable if not m.startswith("RPT_EXP_") and not re.search(r"_(H|HPP)$", m)}
+    assert {"RPT_SLICE_LOG", "RPT_SLICE_SKEW_MULT", "RPT_NT_PART_STORES", "RPT_COMPACT_STAGE"} <= overridable  # the scan works
+    product = re.search(r"#if defined\(RPT_PRODUCT_BUILD\)\n((?:static_assert\(.*?\);\n)+)#endif", open(SRC).read(), re.S).group(1)
+    pinned = set(re.findall(r"\b(RPT_\w+) == \d+", product))
+    assert not (overridable - pinned), "tuning macros the product build does not pin: %s" % sorted(overridable - pinned)
+    assert not (pinned - overridable), "pinned but not overridable (stale): %s" % sorted(pinned - overridable)
 
 
 def test_small_probe_rows_cover_every_segment():

@@ -12,7 +12,7 @@ def test_every_kernel_of_the_host_runtime_has_a_row_or_an_exemption():
     for name in ("slice_probe_kernel", "partition_kernel", "unpermute_sel_kernel", "hash_kernel", "or_slices_kernel(fold)",
                  "probe_bits_masked_hybrid_kernel", "stream_copy_kernel"):
         assert name in source, name
-    assert len(source) >= 35
+    assert len(source) >= 33  # every kernel the host records today
     covered = {kl.base_name(n) for n in kl.expected_names()}
     exempt = set(kl.EXEMPT)
     missing = source - covered - exempt
@@ -24,10 +24,9 @@ def test_every_kernel_of_the_host_runtime_has_a_row_or_an_exemption():
 
 
 def test_exemptions_are_the_agreed_ones_each_with_a_reason():
-    assert set(kl.EXEMPT) == {"or_slices_kernel(allreduce)", "stream_read_kernel", "stream_copy_kernel",
-                              "compact_lookback_kernel", "group_sum_scan_kernel"}
+    assert set(kl.EXEMPT) == {"or_slices_kernel(allreduce)", "stream_read_kernel", "stream_copy_kernel"}
     assert all(isinstance(r, str) and len(r) > 20 for r in kl.EXEMPT.values())
-    assert set(kl.NEVER_LAUNCHED) == {"compact_lookback_kernel", "group_sum_scan_kernel"} <= set(kl.EXEMPT)
+    assert kl.NEVER_LAUNCHED == ()  # no kernel is compiled in but switched off: what the host can record, it launches
 
 
 def test_dispatch_products_are_complete():

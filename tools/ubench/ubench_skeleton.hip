@@ -166,7 +166,7 @@ __global__ __launch_bounds__(T) void skeleton_batched(const u64x2* __restrict__ 
 // the segment's 8 words (count: 4 bytes), so lanes past them are dropped by the range check instead of being skipped
 // by a branch (a skipped store leaves the compiler's memory counter unknown: it waits for everything, s_waitcnt
 // vmcnt(0), before each segment's data)
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32v2 __attribute__((ext_vector_type(2)));
 constexpr int kRsrcWord3 = 0x00020000;  // gfx9 raw buffer: 32-bit data format, no swizzle
 template <int T, int NB>
 __global__ __launch_bounds__(T) void skeleton_bufstore(const u64x2* __restrict__ keys, uint64_t n_segs,
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(T) void skeleton_bufstore(const u64x2* __restrict__
 #pragma unroll
         for (int j = 0; j < 8; j++) mine = lane == static_cast<uint32_t>(j) ? word[j] : mine;
         const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(bits + seg * 8, 0, 64, kRsrcWord3);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{static_cast<uint32_t>(mine), static_cast<uint32_t>(mine >> 32)}, rw,
+        __builtin_amdgcn_raw_buffer_store_b64(u32v2{static_cast<uint32_t>(mine), static_cast<uint32_t>(mine >> 32)}, rw,
                                               static_cast<int>(lane * 8), 0, 0);
         const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(counts + seg, 0, 4, kRsrcWord3);
         __builtin_amdgcn_raw_buffer_store_b32(cnt, rc, static_cast<int>(lane * 4), 0, 0);
