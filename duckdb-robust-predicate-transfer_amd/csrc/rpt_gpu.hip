@@ -52,6 +52,7 @@
 #include "kernels/compaction.hpp"
 #include "kernels/misc.hpp"
 #include "kernels/insert_masked.hpp"
+#include "kernels/partition_masked.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_LDS_HYBRID_MAX_LOG
@@ -935,6 +936,8 @@ void launch_bucket_scatter_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a
     }                                                        \
   } while (0)
 
+#include "rpt_routed_insert.hpp"  // the masked partition pass of the routed device-side inserts
+
 // [rows][cols] u32 matrix -> [cols][rows] (the run-table transpose kernel).
 int transpose_u32(hipStream_t s, const uint32_t* in, uint64_t rows, uint64_t cols, uint32_t* out, uint32_t* heavy = nullptr,
                   uint32_t heavy_run = 0, uint32_t epoch = 0) {
@@ -1382,6 +1385,10 @@ int rpt_bf_set_insert_strategy(rpt_bf* bf, int strategy) {
   return RPT_OK;
 }
 
+static int finish_routed_insert(rpt_bf* bf, hipStream_t s, bool captured, const InsertWorkspace& ws, uint64_t n_tiles,
+                                uint32_t tile_slices, uint32_t tm, uint32_t grid_slices, const uint32_t* bucket_tiles,
+                                const uint32_t* l1_error);
+
 int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* workspace, size_t workspace_bytes,
                      rpt_stream_t stream) {
   if (!bf) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter");
@@ -1429,7 +1436,6 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
     std::lock_guard<std::mutex> lk(bf->order_mu);
     if (bf->order_pending) RPT_HIP(hipStreamWaitEvent(s, bf->order_ev, 0));
   }
-  const int cus = num_cus(bf->device);
   const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, nullptr};
   const bool dense = dense_ok(col, nullptr);
   // the partition input: the key column itself, or (bucketed) the level-2 hash array
@@ -1460,10 +1466,22 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
     RPT_DISPATCH_KD(launch_partition_t, col->key_type, dense, static_cast<unsigned>(n_tiles), s, pa, n_part, tile_slices - 1,
                     n_tiles, ws.recs, static_cast<uint16_t*>(nullptr), ws.runs_tm, bf->stats, dev_n_tiles, tm);
   RPT_LAUNCHED("partition_kernel");
-  st = transpose_u32(s, ws.runs_tm, n_tiles, tile_slices, ws.runs);
+  return finish_routed_insert(bf, s, captured, ws, n_tiles, tile_slices, tm, grid_slices, bucket_tiles,
+                              buck ? l1_error_flag(ws.lists, l1_geom(n, L)) : nullptr);
+}
+
+// The tail every routed insert shares (rpt_bf_insert_ws, and the routed device-side inserts below), after its
+// partition pass has left recs and runs_tm in the workspace: the run table transposed, then the slice merge into the
+// words. n_tiles tiles of tm * kTileRows rows over tile_slices slices; grid_slices slices in all (bucketed: every
+// bucket's; bucket_tiles and l1_error are the bucketed insert's, else nullptr). The caller has run
+// RPT_REFUSE_CAPTURE_WRITE and waited for the filter's previous write.
+static int finish_routed_insert(rpt_bf* bf, hipStream_t s, bool captured, const InsertWorkspace& ws, uint64_t n_tiles,
+                                uint32_t tile_slices, uint32_t tm, uint32_t grid_slices, const uint32_t* bucket_tiles,
+                                const uint32_t* l1_error) {
+  const int st = transpose_u32(s, ws.runs_tm, n_tiles, tile_slices, ws.runs);
   if (st != RPT_OK) return st;
-  const uint32_t splits = static_cast<uint32_t>(
-      std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, static_cast<uint64_t>(cus) / grid_slices)));
+  const uint32_t splits = static_cast<uint32_t>(std::max<uint64_t>(
+      1, std::min<uint64_t>(n_tiles, static_cast<uint64_t>(num_cus(bf->device)) / grid_slices)));
   // only the slice merge writes the words: it alone is ordered after the filter's previous writes
   WriteOrder order(bf, s);
   RPT_REFUSE_IN_FLIGHT(order, "write");
@@ -1483,10 +1501,10 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
   hipLaunchKernelGGL(rpt::slice_insert_kernel, dim3(grid_slices * splits), dim3(rpt::kSliceThreads), 0, s, bf->words, splits,
                      n_tiles, ws.recs, ws.runs, static_cast<uint32_t>(rpt::tile_cap_for(tile_slices, tm)), bucket_tiles, mode);
   prof_i.end();
-  if (buck) {  // a level-1 bound hit (never expected): every bit set instead of keys missing
-    const uint64_t n_words = 1ULL << L;
+  if (l1_error != nullptr) {  // a level-1 bound hit (never expected): every bit set instead of keys missing
+    const uint64_t n_words = 1ULL << bf->log_num_blocks;
     hipLaunchKernelGGL(rpt::l1_error_fill_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(ceil_div(n_words, rpt::kErrorFillThreads * 8ULL), 4096))),
-                       dim3(rpt::kErrorFillThreads), 0, s, bf->words, n_words, l1_error_flag(ws.lists, l1_geom(n, L)));
+                       dim3(rpt::kErrorFillThreads), 0, s, bf->words, n_words, l1_error);
   }
   const hipError_t el = hipGetLastError();
   if (store_all && el == hipSuccess) bf->clear_pending.store(false);  // the slice stores zeroed the words
@@ -1494,6 +1512,87 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
   if (el != hipSuccess) return fail(RPT_ERR_HIP, "slice_insert_kernel launch: %s", hipGetErrorString(el));
   RPT_LAUNCHED("slice_insert_kernel");
   return RPT_OK;
+}
+
+// ---- routed device-side inserts (kernels/partition_masked.hpp) ------------------------------------------------
+// Does a device-side insert of n (/ max_rows) rows into bf route (*routed: the strategy resolves to PARTITIONED),
+// and if so, can it: the filter size, then the workspace (too small: RPT_ERR_WORKSPACE; misaligned:
+// RPT_ERR_INVALID_ARGUMENT). ATOMIC and BUCKETED do not route and look at no workspace. Enqueues nothing.
+static int check_routed_insert(const rpt_bf* bf, uint64_t n, const void* workspace, size_t workspace_bytes, bool* routed) {
+  const int L = bf->log_num_blocks;
+  *routed = resolve_insert_strategy(bf->insert_strategy.load(), L, n) == RPT_INSERT_PARTITIONED;
+  if (!*routed) return RPT_OK;
+  if (!strategy_supported(RPT_PROBE_PARTITIONED, L))
+    return fail(RPT_ERR_INVALID_ARGUMENT, "partitioned insert unsupported for a 2^%d-block filter", L);
+  const size_t need = insert_workspace_layout(n, L, RPT_INSERT_PARTITIONED, nullptr, nullptr);
+  if (!workspace || workspace_bytes < need)
+    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
+  return RPT_OK;
+}
+
+// enqueue_device_rows_insert's routed twin: the masked partition pass over all n rows (a row that is not selected
+// emits no record), then rpt_bf_insert_ws's tail. The caller has validated the arguments (check_routed_insert said
+// `routed`), made the filter's device current and run RPT_REFUSE_CAPTURE_WRITE. n > 0.
+static int enqueue_routed_rows_insert(rpt_bf* bf, const rpt_key_column* col, const uint64_t* bits, const uint32_t* sel,
+                                      const uint64_t* count_dev, uint64_t n, void* workspace, hipStream_t s) {
+  const int L = bf->log_num_blocks;
+  const bool captured = stream_capturing(s);
+  bf->has_data.store(1);
+  InsertWorkspace ws;
+  insert_workspace_layout(n, L, RPT_INSERT_PARTITIONED, workspace, &ws);
+  // the partition pass folds the keys' min/max into bf->stats: after the filter's previous write (rpt_bf_insert_ws)
+  if (!captured) {
+    std::lock_guard<std::mutex> lk(bf->order_mu);
+    if (bf->order_pending) RPT_HIP(hipStreamWaitEvent(s, bf->order_ev, 0));
+  }
+  const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, sel};
+  const uint32_t slices = slice_count(L), tm = tile_mult_of(slices);
+  const uint64_t n_tiles = ceil_div(n, rpt::kTileRows * tm);
+  if (bits != nullptr)
+    RPT_DISPATCH_KD(launch_partition_bits_t, col->key_type, dense_ok(col, sel), static_cast<unsigned>(n_tiles), s, a, n,
+                    slices - 1, ws.recs, ws.runs_tm, bf->stats, bits, tm);
+  else
+    RPT_DISPATCH_KD(launch_partition_sel_t, col->key_type, false, static_cast<unsigned>(n_tiles), s, a, n, slices - 1,
+                    ws.recs, ws.runs_tm, bf->stats, count_dev, tm);
+  RPT_LAUNCHED("partition_masked_kernel");
+  return finish_routed_insert(bf, s, captured, ws, n_tiles, slices, tm, slices, nullptr, nullptr);
+}
+
+int rpt_bf_insert_bits_ws(rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
+                          const uint64_t* row_bits, void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  if (!bf) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter");
+  if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
+  if (n == 0) return RPT_OK;
+  int st = check_col(col);
+  if (st != RPT_OK) return st;
+  if (!row_bits) return fail(RPT_ERR_INVALID_ARGUMENT, "null row_bits");
+  bool routed = false;
+  st = check_routed_insert(bf, n, workspace, workspace_bytes, &routed);
+  if (st != RPT_OK) return st;
+  RPT_ON_DEVICE(bf->device);
+  RPT_REFUSE_CAPTURE_WRITE(bf, as_stream(stream), "insert");
+  if (!routed) return enqueue_device_rows_insert(bf, col, row_bits, row_sel, nullptr, n, as_stream(stream));
+  return enqueue_routed_rows_insert(bf, col, row_bits, row_sel, nullptr, n, workspace, as_stream(stream));
+}
+
+int rpt_bf_insert_sel_ws(rpt_bf* bf, const rpt_key_column* col, const uint32_t* sel, const uint64_t* count_dev,
+                         uint64_t max_rows, void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  if (!bf) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter");
+  if (max_rows >= (1ULL << 32))
+    return fail(RPT_ERR_INVALID_ARGUMENT, "max_rows=%llu rows exceeds uint32 sel_t", (unsigned long long)max_rows);
+  if (max_rows == 0) return RPT_OK;
+  int st = check_col(col);
+  if (st != RPT_OK) return st;
+  if (!sel) return fail(RPT_ERR_INVALID_ARGUMENT, "null sel");
+  if (!count_dev) return fail(RPT_ERR_INVALID_ARGUMENT, "null count_dev");
+  bool routed = false;
+  st = check_routed_insert(bf, max_rows, workspace, workspace_bytes, &routed);
+  if (st != RPT_OK) return st;
+  RPT_ON_DEVICE(bf->device);
+  RPT_REFUSE_CAPTURE_WRITE(bf, as_stream(stream), "insert");
+  if (!routed) return enqueue_device_rows_insert(bf, col, nullptr, sel, count_dev, max_rows, as_stream(stream));
+  return enqueue_routed_rows_insert(bf, col, nullptr, sel, count_dev, max_rows, workspace, as_stream(stream));
 }
 
 int rpt_bf_find_bits(const rpt_bf* bf, const rpt_key_column* col, uint64_t n, uint64_t* out_bits,
@@ -1961,10 +2060,14 @@ int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* co
                              stream, nullptr);
 }
 
-int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
-                       rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
-                       const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
-                       void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+// The body of rpt_bf_transfer_ws and rpt_bf_transfer_insert_ws. route: a destination whose insert strategy resolves
+// to PARTITIONED for n takes the routed insert through insert_workspace (rpt_bf_transfer_insert_ws); otherwise every
+// destination takes one atomic OR per row and insert_workspace is not looked at (rpt_bf_transfer_ws).
+static int transfer_impl(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                         rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                         const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                         void* workspace, size_t workspace_bytes, bool route, void* insert_workspace,
+                         size_t insert_workspace_bytes, rpt_stream_t stream) {
   if (!filters || !cols || !out_count_dev || !dst_filters || !dst_cols)
     return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
   if (n_filters == 0 || n_filters > RPT_MAX_CHAIN)
@@ -1990,6 +2093,13 @@ int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols,
     st = check_col(&dst_cols[j]);
     if (st != RPT_OK) return st;
   }
+  // which destinations route, and their share of the insert workspace (they run one after another on the stream)
+  bool routed[RPT_MAX_CHAIN] = {};
+  if (route && n > 0)
+    for (uint32_t j = 0; j < n_dst; j++) {
+      st = check_routed_insert(dst_filters[j], n, insert_workspace, insert_workspace_bytes, &routed[j]);
+      if (st != RPT_OK) return st;
+    }
   RPT_ON_DEVICE(device);
   hipStream_t s = as_stream(stream);
   // every destination's capture and in-flight check before the chain enqueues anything (n == 0 writes none)
@@ -2002,11 +2112,45 @@ int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols,
   // the survivors into the outgoing filters: from the accumulated bits (rows row_sel[i] of dst_cols[j], as probed),
   // or, after the hand-over, from out_sel, which holds the same row ids
   for (uint32_t j = 0; j < n_dst; j++) {
-    st = bits != nullptr ? enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, s)
-                         : enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], nullptr, out_sel, out_count_dev, n, s);
+    if (bits == nullptr)
+      st = enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], nullptr, out_sel, out_count_dev, n, s);
+    else if (routed[j])
+      st = enqueue_routed_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, insert_workspace, s);
+    else
+      st = enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, s);
     if (st != RPT_OK) return st;
   }
   return RPT_OK;
+}
+
+int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                       rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                       const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                       void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  return transfer_impl(filters, cols, n_filters, dst_filters, dst_cols, n_dst, row_sel, n, out_sel, out_count_dev,
+                       workspace, workspace_bytes, false, nullptr, 0, stream);
+}
+
+size_t rpt_bf_transfer_insert_workspace_bytes(rpt_bf* const* dst_filters, uint32_t n_dst, uint64_t n_rows) {
+  if (!dst_filters || n_dst == 0 || n_dst > RPT_MAX_CHAIN || n_rows >= (1ULL << 32)) return 0;
+  size_t need = 0;
+  for (uint32_t j = 0; j < n_dst; j++) {
+    if (!dst_filters[j]) return 0;
+    const int L = dst_filters[j]->log_num_blocks;
+    if (resolve_insert_strategy(dst_filters[j]->insert_strategy.load(), L, n_rows) == RPT_INSERT_PARTITIONED &&
+        strategy_supported(RPT_PROBE_PARTITIONED, L))
+      need = std::max(need, insert_workspace_layout(n_rows, L, RPT_INSERT_PARTITIONED, nullptr, nullptr));
+  }
+  return need;
+}
+
+int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                              rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                              const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                              void* workspace, size_t workspace_bytes, void* insert_workspace,
+                              size_t insert_workspace_bytes, rpt_stream_t stream) {
+  return transfer_impl(filters, cols, n_filters, dst_filters, dst_cols, n_dst, row_sel, n, out_sel, out_count_dev,
+                       workspace, workspace_bytes, true, insert_workspace, insert_workspace_bytes, stream);
 }
 
 

@@ -34,6 +34,8 @@ from .bloom import (  # noqa: F401
     probe_chain_ws,
     synth_build_keys,
     synth_probe_keys,
+    transfer_insert_workspace_bytes,
+    transfer_insert_ws,
     transfer_ws,
     validity_from_mask,
     words_or_slices,

@@ -163,6 +163,64 @@ def transfer_ws(filters, columns, dst_filters, dst_columns, *, row_sel: Optional
     return out_sel, out_count
 
 
+def transfer_insert_workspace_bytes(dst_filters, n: int) -> int:
+    """Insert workspace transfer_insert_ws needs for these destinations and n rows: the largest need of the
+    destinations whose insert strategy routes for n, 0 if none does (rpt_bf_transfer_insert_workspace_bytes)."""
+    if not dst_filters:
+        raise RptError(1, "at least one destination filter")
+    handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
+    return int(dst_filters[0]._lib.rpt_bf_transfer_insert_workspace_bytes(handles, len(dst_filters), int(n)))
+
+
+def transfer_insert_ws(filters, columns, dst_filters, dst_columns, *, row_sel: Optional[torch.Tensor] = None,
+                       n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+                       out_count: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                       insert_workspace: Optional[torch.Tensor] = None, stream=None):
+    """transfer_ws with each destination's insert strategy honoured (rpt_bf_transfer_insert_ws): a destination that
+    resolves to RPT_INSERT_PARTITIONED for n rows takes the routed insert (partition, LDS slice merge) from the
+    survivors' result bits, the others one atomic OR per row. Arguments and result as transfer_ws, plus the insert
+    workspace of transfer_insert_workspace_bytes(dst_filters, n) bytes the destinations share (allocated here when
+    None). Nothing is read back."""
+    if not filters or len(filters) != len(columns):
+        raise RptError(1, "one key column per filter, at least one filter")
+    if not dst_filters or len(dst_filters) != len(dst_columns):
+        raise RptError(1, "one key column per destination filter, at least one destination")
+    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
+    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
+    if n is None:
+        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
+        n = (row_sel.numel() if row_sel is not None else
+             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
+    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+        raise RptError(1, "row_sel must be a 32-bit device tensor")
+    device = filters[0].device
+    lib = filters[0]._lib
+    if out_sel is None:
+        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    if out_count is None:
+        out_count = torch.zeros(1, dtype=torch.int64, device=device)
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
+    if workspace is None:
+        need = int(lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            workspace.record_stream(stream)  # freed on return while the transfer may still run on `stream`
+    if insert_workspace is None:
+        need = int(lib.rpt_bf_transfer_insert_workspace_bytes(dst_handles, len(dst_filters), n))
+        insert_workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            insert_workspace.record_stream(stream)
+    arr = (KeyColumn * len(cols))(*cols)
+    darr = (KeyColumn * len(dcols))(*dcols)
+    check(lib.rpt_bf_transfer_insert_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters), _ptr(row_sel),
+                                        n, out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
+                                        workspace.numel() * workspace.element_size(), insert_workspace.data_ptr(),
+                                        insert_workspace.numel() * insert_workspace.element_size(),
+                                        _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,
                 validity: Optional[torch.Tensor] = None) -> KeyColumn:
     """rpt_key_column for a FLAT (key_sel None) or DICTIONARY (key_sel uint32/int32) key vector."""
@@ -365,6 +423,60 @@ class BloomFilter:
             raise RptError(1, f"max_rows={max_rows} exceeds the {sel.numel()} entries of sel")
         check(self._lib.rpt_bf_insert_sel(self._h, ctypes.byref(col), sel.data_ptr(), count.data_ptr(), max_rows,
                                           _stream(self.device, stream)), self._lib)
+
+    def _insert_workspace(self, n: int, workspace: Optional[torch.Tensor], stream):
+        """(pointer, bytes) of the workspace a routed device-side insert of n rows gets: the caller's, or one of
+        rpt_bf_insert_workspace_bytes(n) bytes allocated here (none when the strategy for n does not route)."""
+        if workspace is None:
+            need = int(self._lib.rpt_bf_insert_workspace_bytes(self._h, n))
+            if not need:
+                return None, 0
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if isinstance(stream, torch.cuda.Stream):
+                workspace.record_stream(stream)  # freed on return while the insert may still run on `stream`
+        return workspace.data_ptr(), workspace.numel() * workspace.element_size()
+
+    def insert_bits_ws(self, keys: torch.Tensor, bits: torch.Tensor, *, n: Optional[int] = None,
+                       row_sel: Optional[torch.Tensor] = None, key_type: Optional[int] = None, key_sel=None,
+                       validity=None, workspace: Optional[torch.Tensor] = None, stream=None,
+                       strategy: Optional[int] = None) -> None:
+        """insert_bits with the filter's insert strategy honoured (rpt_bf_insert_bits_ws): where it resolves to
+        RPT_INSERT_PARTITIONED for n rows, the selected rows are partitioned by filter slice and merged through
+        LDS instead of one atomic OR per row; the result is identical. `workspace`: device bytes of
+        rpt_bf_insert_workspace_bytes(n) (allocated here when None); strategy: as insert()."""
+        if n is None:
+            n = row_sel.numel() if row_sel is not None else (key_sel.numel() if key_sel is not None else keys.numel())
+        col = make_column(keys, key_type, key_sel, validity)
+        if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+            raise RptError(1, "row_sel must be a 32-bit device tensor")
+        need = ((n + SEG_ROWS - 1) // SEG_ROWS) * (SEG_ROWS // 64)
+        if not bits.is_cuda or not bits.is_contiguous() or bits.element_size() != 8 or bits.numel() < need:
+            raise RptError(1, f"bits must be a contiguous device tensor of at least {need} 64-bit words")
+        if strategy is not None:
+            check(self._lib.rpt_bf_set_insert_strategy(self._h, int(strategy)))
+        ws_ptr, ws_bytes = self._insert_workspace(n, workspace, stream)
+        check(self._lib.rpt_bf_insert_bits_ws(self._h, ctypes.byref(col), _ptr(row_sel), n, bits.data_ptr(), ws_ptr,
+                                              ws_bytes, _stream(self.device, stream)), self._lib)
+
+    def insert_sel_ws(self, keys: torch.Tensor, sel: torch.Tensor, count: torch.Tensor, *,
+                      max_rows: Optional[int] = None, key_type: Optional[int] = None, key_sel=None, validity=None,
+                      workspace: Optional[torch.Tensor] = None, stream=None, strategy: Optional[int] = None) -> None:
+        """insert_sel with the filter's insert strategy honoured (rpt_bf_insert_sel_ws), resolved with max_rows:
+        the count stays on the device. `workspace`: device bytes of rpt_bf_insert_workspace_bytes(max_rows)
+        (allocated here when None); strategy: as insert()."""
+        col = make_column(keys, key_type, key_sel, validity)
+        if not sel.is_cuda or not sel.is_contiguous() or sel.element_size() != 4:
+            raise RptError(1, "sel must be a contiguous 32-bit device tensor")
+        if not count.is_cuda or count.element_size() != 8 or count.numel() < 1:
+            raise RptError(1, "count must be a 64-bit device tensor")
+        max_rows = sel.numel() if max_rows is None else int(max_rows)
+        if max_rows > sel.numel():
+            raise RptError(1, f"max_rows={max_rows} exceeds the {sel.numel()} entries of sel")
+        if strategy is not None:
+            check(self._lib.rpt_bf_set_insert_strategy(self._h, int(strategy)))
+        ws_ptr, ws_bytes = self._insert_workspace(max_rows, workspace, stream)
+        check(self._lib.rpt_bf_insert_sel_ws(self._h, ctypes.byref(col), sel.data_ptr(), count.data_ptr(), max_rows,
+                                             ws_ptr, ws_bytes, _stream(self.device, stream)), self._lib)
 
     def reinitialize(self, actual_rows: int) -> None:
         check(self._lib.rpt_bf_reinitialize(self._h, int(actual_rows)))

@@ -346,7 +346,7 @@ int rpt_keys_widen(const uint32_t* lo, const uint32_t* chunk_hi, const uint32_t*
  *
  * All three: the filter ends up bit-identical to rpt_bf_insert of exactly the selected rows (ORed into what it
  *   holds; the min/max of the selected valid I32/I64 keys folded in; a selected NULL row inserts NULL_HASH). One
- *   atomic OR per row, whatever the filter's insert strategy: the routed inserts need their row count on the host.
+ *   atomic OR per row, whatever the filter's insert strategy (the *_ws variants below route).
  *   Stream-ordered: no synchronisation, no copy back, no allocation. Writes follow rpt_bf_insert's rules
  *   (rpt_bf_settle above): ordered after the filter's previous write; a deferred clear is settled first outside a
  *   capture and refused inside one; a captured call ORs its rows at every replay.
@@ -363,6 +363,38 @@ int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols,
                        rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
                        const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
                        void* workspace, size_t workspace_bytes, rpt_stream_t stream);
+
+/* The same three with the destination's insert strategy honoured (rpt_bf_insert_strategy_for(bf, n) resolved with
+ * n / max_rows, the only row count the host has; rpt_bf_set_insert_strategy is honoured):
+ *   PARTITIONED  a partition pass over all n rows in which a row that is not selected emits no record (a 512-row
+ *                segment without a selected row loads no key; a tile without one stores no record), then
+ *                rpt_bf_insert_ws's run-table transpose and LDS slice merge. No count reaches the host: the tile
+ *                geometry depends on n only. Needs rpt_bf_insert_workspace_bytes(bf, n) bytes of device workspace
+ *                (16-byte aligned; contents on entry do not matter; nothing past that size is written). Too small:
+ *                RPT_ERR_WORKSPACE; misaligned: RPT_ERR_INVALID_ARGUMENT; both before any launch.
+ *   ATOMIC, BUCKETED  the calls above, one atomic OR per row; the workspace is not looked at and may be null. A
+ *                bucketed masked insert does not exist: its level 1 sizes lists from the row count and would need a
+ *                second design.
+ * The result, has_data, the argument checks and the write rules are those of the calls above; the slice merge picks
+ * its mode as rpt_bf_insert_ws does (every slice stored whole under a deferred clear, plain stores into a pristine
+ * filter, else adaptive; atomics when a slice is split over workgroups or the call is captured).
+ * rpt_bf_transfer_insert_ws: rpt_bf_transfer_ws with one more workspace, shared by the destinations, which run one
+ *   after another on the stream: a destination that resolves to PARTITIONED for n takes the routed insert from the
+ *   accumulated result bits, the others one atomic OR per row. rpt_bf_transfer_insert_workspace_bytes returns the
+ *   largest need over the destinations (0 if none routes, and 0 on null / invalid arguments). The small-batch
+ *   hand-over is rpt_bf_transfer_ws's (from out_sel, one atomic OR per row; the insert workspace is checked all the
+ *   same). Every destination check runs before the chain enqueues anything. insert_workspace must not overlap
+ *   workspace. Callers pick the entry point: nothing switches between the two by survivor fraction. */
+int rpt_bf_insert_bits_ws(rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
+                          const uint64_t* row_bits, void* workspace, size_t workspace_bytes, rpt_stream_t stream);
+int rpt_bf_insert_sel_ws(rpt_bf* bf, const rpt_key_column* col, const uint32_t* sel, const uint64_t* count_dev,
+                         uint64_t max_rows, void* workspace, size_t workspace_bytes, rpt_stream_t stream);
+size_t rpt_bf_transfer_insert_workspace_bytes(rpt_bf* const* dst_filters, uint32_t n_dst, uint64_t n_rows);
+int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                              rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                              const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                              void* workspace, size_t workspace_bytes, void* insert_workspace,
+                              size_t insert_workspace_bytes, rpt_stream_t stream);
 
 /* ---- merge / fold / export ----------------------------------------------------------------- */
 /* dst |= src (same log_num_blocks, same device): merging per-thread or per-GPU partial filters
