@@ -161,6 +161,7 @@ bool flatten_converted(const Vector& v, uint64_t count, uint8_t* keys, uint64_t*
 // 16-B stores, which skip the read-for-ownership of every destination line a plain memcpy of a 16 KiB vector
 // does (the staging buffer is not read back by the host), then a store fence so the DMA sees the bytes.
 void copy_to_staging(uint8_t* dst, const void* src_v, size_t bytes) {
+  if (bytes == 0) return;  // an empty chunk's data pointer may be null, which memcpy must not be given
   const uint8_t* src = static_cast<const uint8_t*>(src_v);
   const size_t head = std::min(bytes, static_cast<size_t>((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15));
   if (bytes < 256) {
