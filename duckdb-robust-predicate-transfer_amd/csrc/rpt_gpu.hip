@@ -53,6 +53,7 @@
 #include "kernels/misc.hpp"
 #include "kernels/insert_masked.hpp"
 #include "kernels/partition_masked.hpp"
+#include "kernels/probe_sel.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_LDS_HYBRID_MAX_LOG
@@ -1969,6 +1970,49 @@ size_t rpt_bf_probe_chain_workspace_bytes(const rpt_bf* const* filters, uint32_t
   return chain_workspace_layout(filters, n_filters, n_rows, nullptr, nullptr);
 }
 
+// The stages after the first of a workspace chain (filters[1 .. n_filters)), each ANDing its filter's result into the
+// accumulated bits ws.bits / ws.seg_counts of n rows in place. strategy[f]: filter f's resolved probe strategy.
+static int enqueue_chain_later_stages(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                      const int* strategy, const uint32_t* row_sel, uint64_t n, const ChainWorkspace& ws,
+                                      int device, rpt_stream_t stream) {
+  hipStream_t s = as_stream(stream);
+  const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
+  int st = RPT_OK;
+  bool done = false;
+  for (uint32_t f = 1; f < n_filters; f++) {
+    const rpt_bf* bf = filters[f];
+    const rpt_key_column* col = &cols[f];
+    if (routed(strategy[f])) {
+      // the whole batch through the stage's phase 1 (dead rows are partitioned too: routing only the survivors
+      // would need their count on the host), then one AND + recount
+      st = probe_phase1_impl(bf, col, row_sel, n, ws.stage, ws.stage_bytes, stream, nullptr, nullptr, &done, ws.tmp_bits);
+      if (st != RPT_OK) return st;
+      const uint64_t n_units = n_segs * (rpt::kWordsPerSeg / 2);
+      const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(
+          1, std::min<uint64_t>(ceil_div(n_units, rpt::kBlockThreads), static_cast<uint64_t>(num_cus(device)) * rpt::kBlocksPerCU)));
+      ProfScope prof("bits_and_count_kernel", s);
+      hipLaunchKernelGGL(rpt::bits_and_count_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, s, ws.bits, ws.tmp_bits,
+                         n_segs, ws.seg_counts);
+      prof.end();
+      RPT_LAUNCHED("bits_and_count_kernel");
+      continue;
+    }
+    const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
+    const bool dense = dense_ok(col, row_sel);
+    if (strategy[f] == RPT_PROBE_GATHER) {
+      const unsigned grid = persistent_grid(device, n_segs);
+      RPT_DISPATCH_KD(launch_probe_bits_masked_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
+      RPT_LAUNCHED("probe_bits_masked_kernel");
+    } else {  // RPT_PROBE_LDS
+      const unsigned grid = lds_probe_grid(device, bf->log_num_blocks, n_segs);
+      RPT_DISPATCH_KD(launch_probe_bits_masked_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits,
+                      ws.seg_counts);
+      RPT_LAUNCHED("probe_bits_masked_kernel<lds>");
+    }
+  }
+  return RPT_OK;
+}
+
 // The body of rpt_bf_probe_chain_ws, shared with rpt_bf_transfer_ws. *survivor_bits (nullable) tells the caller where
 // the survivors are once the call is enqueued: the accumulated result bits in the workspace (the workspace path), or
 // nullptr when only out_sel / *out_count_dev hold them (the small-batch hand-over) or nothing was probed (n == 0).
@@ -2017,37 +2061,8 @@ static int probe_chain_ws_impl(const rpt_bf* const* filters, const rpt_key_colum
   st = probe_phase1_impl(filters[0], &cols[0], row_sel, n, ws.stage, ws.stage_bytes, stream, nullptr, nullptr, &done,
                          ws.bits, ws.seg_counts);
   if (st != RPT_OK) return st;
-  for (uint32_t f = 1; f < n_filters; f++) {
-    const rpt_bf* bf = filters[f];
-    const rpt_key_column* col = &cols[f];
-    if (routed(strategy[f])) {
-      // the whole batch through the stage's phase 1 (dead rows are partitioned too: routing only the survivors
-      // would need their count on the host), then one AND + recount
-      st = probe_phase1_impl(bf, col, row_sel, n, ws.stage, ws.stage_bytes, stream, nullptr, nullptr, &done, ws.tmp_bits);
-      if (st != RPT_OK) return st;
-      const uint64_t n_units = n_segs * (rpt::kWordsPerSeg / 2);
-      const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(
-          1, std::min<uint64_t>(ceil_div(n_units, rpt::kBlockThreads), static_cast<uint64_t>(num_cus(device)) * rpt::kBlocksPerCU)));
-      ProfScope prof("bits_and_count_kernel", s);
-      hipLaunchKernelGGL(rpt::bits_and_count_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, s, ws.bits, ws.tmp_bits,
-                         n_segs, ws.seg_counts);
-      prof.end();
-      RPT_LAUNCHED("bits_and_count_kernel");
-      continue;
-    }
-    const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
-    const bool dense = dense_ok(col, row_sel);
-    if (strategy[f] == RPT_PROBE_GATHER) {
-      const unsigned grid = persistent_grid(device, n_segs);
-      RPT_DISPATCH_KD(launch_probe_bits_masked_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
-      RPT_LAUNCHED("probe_bits_masked_kernel");
-    } else {  // RPT_PROBE_LDS
-      const unsigned grid = lds_probe_grid(device, bf->log_num_blocks, n_segs);
-      RPT_DISPATCH_KD(launch_probe_bits_masked_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits,
-                      ws.seg_counts);
-      RPT_LAUNCHED("probe_bits_masked_kernel<lds>");
-    }
-  }
+  st = enqueue_chain_later_stages(filters, cols, n_filters, strategy, row_sel, n, ws, device, stream);
+  if (st != RPT_OK) return st;
   if (survivor_bits) *survivor_bits = ws.bits;
   // the tail, once
   return launch_sel_tail(s, ws.bits, ws.seg_counts, ws.group_sums, ws.group_offs, n_segs, row_sel, out_sel, out_count_dev);
@@ -2058,6 +2073,26 @@ int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* co
                           void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
   return probe_chain_ws_impl(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, workspace, workspace_bytes,
                              stream, nullptr);
+}
+
+// A chain's survivors of n rows into the outgoing filters: from the accumulated bits (rows row_sel[i] of dst_cols[j], as
+// probed; routed[j]: the routed insert through insert_workspace), or, with bits == nullptr (after the small-batch
+// hand-over), from out_sel / *out_count_dev, which hold the same row ids.
+static int enqueue_transfer_inserts(rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                                    const bool* routed, const uint64_t* bits, const uint32_t* row_sel,
+                                    const uint32_t* out_sel, const uint64_t* out_count_dev, uint64_t n,
+                                    void* insert_workspace, hipStream_t s) {
+  for (uint32_t j = 0; j < n_dst; j++) {
+    int st;
+    if (bits == nullptr)
+      st = enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], nullptr, out_sel, out_count_dev, n, s);
+    else if (routed[j])
+      st = enqueue_routed_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, insert_workspace, s);
+    else
+      st = enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, s);
+    if (st != RPT_OK) return st;
+  }
+  return RPT_OK;
 }
 
 // The body of rpt_bf_transfer_ws and rpt_bf_transfer_insert_ws. route: a destination whose insert strategy resolves
@@ -2111,16 +2146,8 @@ static int transfer_impl(const rpt_bf* const* filters, const rpt_key_column* col
   if (st != RPT_OK || n == 0) return st;
   // the survivors into the outgoing filters: from the accumulated bits (rows row_sel[i] of dst_cols[j], as probed),
   // or, after the hand-over, from out_sel, which holds the same row ids
-  for (uint32_t j = 0; j < n_dst; j++) {
-    if (bits == nullptr)
-      st = enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], nullptr, out_sel, out_count_dev, n, s);
-    else if (routed[j])
-      st = enqueue_routed_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, insert_workspace, s);
-    else
-      st = enqueue_device_rows_insert(dst_filters[j], &dst_cols[j], bits, row_sel, nullptr, n, s);
-    if (st != RPT_OK) return st;
-  }
-  return RPT_OK;
+  return enqueue_transfer_inserts(dst_filters, dst_cols, n_dst, routed, bits, row_sel, out_sel, out_count_dev, n,
+                                  insert_workspace, s);
 }
 
 int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
@@ -2152,6 +2179,8 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
   return transfer_impl(filters, cols, n_filters, dst_filters, dst_cols, n_dst, row_sel, n, out_sel, out_count_dev,
                        workspace, workspace_bytes, true, insert_workspace, insert_workspace_bytes, stream);
 }
+
+#include "rpt_probe_sel.hpp"  // the device-counted probes: a chain over a selection vector with a device-side count
 
 
 int rpt_hash_combine(const rpt_key_column* col, uint64_t n, uint64_t* inout_hashes, rpt_stream_t stream) {

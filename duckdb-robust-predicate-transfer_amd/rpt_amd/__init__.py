@@ -30,12 +30,16 @@ from .bloom import (  # noqa: F401
     make_column,
     needs_resize,
     probe_chain,
+    probe_chain_sel_workspace_bytes,
+    probe_chain_sel_ws,
     probe_chain_workspace_bytes,
     probe_chain_ws,
     synth_build_keys,
     synth_probe_keys,
+    transfer_insert_sel_ws,
     transfer_insert_workspace_bytes,
     transfer_insert_ws,
+    transfer_sel_ws,
     transfer_ws,
     validity_from_mask,
     words_or_slices,

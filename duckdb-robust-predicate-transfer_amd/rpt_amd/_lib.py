@@ -137,6 +137,23 @@ SIGNATURES = {
         [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p,
          c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
     ),
+    "rpt_bf_probe_sel_strategy_for": (c_int, [c_void_p, c_uint64]),
+    "rpt_bf_probe_chain_sel_workspace_bytes": (c_size_t, [c_void_p, c_uint32, c_uint64]),
+    "rpt_bf_probe_chain_sel_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t,
+         c_void_p],
+    ),
+    "rpt_bf_transfer_sel_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p, c_uint64,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "rpt_bf_transfer_insert_sel_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p, c_uint64,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
+    ),
     "rpt_bf_probe_phase1": (
         c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_size_t, c_void_p]
     ),

@@ -221,6 +221,98 @@ def transfer_insert_ws(filters, columns, dst_filters, dst_columns, *, row_sel: O
     return out_sel, out_count
 
 
+def probe_chain_sel_workspace_bytes(filters, max_rows: int) -> int:
+    """Device workspace the device-counted calls need for a selection of max_rows entries
+    (rpt_bf_probe_chain_sel_workspace_bytes): result bits, segment counts and the tail's sums; no stage area."""
+    if not filters:
+        raise RptError(1, "at least one filter")
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    return int(filters[0]._lib.rpt_bf_probe_chain_sel_workspace_bytes(handles, len(filters), int(max_rows)))
+
+
+def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, workspace):
+    """The checked arguments the three device-counted calls share; every buffer is the caller's (nothing is allocated
+    here, so the calls can be captured into a graph)."""
+    if not filters or len(filters) != len(columns):
+        raise RptError(1, "one key column per filter, at least one filter")
+    for name, t in (("sel", sel), ("out_sel", out_sel)):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4:
+            raise RptError(1, f"{name} must be a contiguous 32-bit device tensor")
+    for name, t in (("count", count), ("out_count", out_count)):
+        if not t.is_cuda or t.element_size() != 8 or t.numel() < 1:
+            raise RptError(1, f"{name} must be a 64-bit device tensor")
+    if not workspace.is_cuda or not workspace.is_contiguous():
+        raise RptError(1, "workspace must be a contiguous device tensor")
+    max_rows = sel.numel() if max_rows is None else int(max_rows)
+    if max_rows > sel.numel() or max_rows > out_sel.numel():
+        raise RptError(1, f"max_rows={max_rows} exceeds the entries of sel ({sel.numel()}) or out_sel ({out_sel.numel()})")
+    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    arr = (KeyColumn * len(cols))(*cols)
+    return handles, arr, max_rows, workspace.numel() * workspace.element_size()
+
+
+def probe_chain_sel_ws(filters, columns, sel: torch.Tensor, count: torch.Tensor, *, out_sel: torch.Tensor,
+                       out_count: torch.Tensor, workspace: torch.Tensor, max_rows: Optional[int] = None, stream=None):
+    """Probe the survivors of an earlier probe again without their count reaching the host
+    (rpt_bf_probe_chain_sel_ws): rows sel[0 .. min(count, max_rows)) of every columns[f] through filters[f]; `sel` and
+    `count` are what probe_async / probe_chain_ws / transfer_ws left on the device, max_rows the capacity of sel
+    (default: its length). out_sel (>= max_rows entries, not overlapping sel), out_count (may be `count` itself) and
+    workspace (probe_chain_sel_workspace_bytes(filters, max_rows) bytes) are the caller's. Never reads the count back
+    and never synchronizes: returns the device tensors (out_sel, out_count)."""
+    handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count,
+                                                      workspace)
+    device, lib = filters[0].device, filters[0]._lib
+    check(lib.rpt_bf_probe_chain_sel_ws(handles, arr, len(filters), sel.data_ptr(), count.data_ptr(), max_rows,
+                                        out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(), ws_bytes,
+                                        _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_sel_ws(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, count: torch.Tensor, *,
+                    out_sel: torch.Tensor, out_count: torch.Tensor, workspace: torch.Tensor,
+                    max_rows: Optional[int] = None, stream=None):
+    """probe_chain_sel_ws, then the survivors inserted into dst_filters[j] on dst_columns[j] (rpt_bf_transfer_sel_ws):
+    the backward pass of predicate transfer over a device-resident table. One atomic OR per row. Arguments and result
+    as probe_chain_sel_ws; the destination columns are indexed by the same row ids as the probed ones."""
+    if not dst_filters or len(dst_filters) != len(dst_columns):
+        raise RptError(1, "one key column per destination filter, at least one destination")
+    handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count,
+                                                      workspace)
+    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
+    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
+    darr = (KeyColumn * len(dcols))(*dcols)
+    device, lib = filters[0].device, filters[0]._lib
+    check(lib.rpt_bf_transfer_sel_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters), sel.data_ptr(),
+                                     count.data_ptr(), max_rows, out_sel.data_ptr(), out_count.data_ptr(),
+                                     workspace.data_ptr(), ws_bytes, _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_insert_sel_ws(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, count: torch.Tensor, *,
+                           out_sel: torch.Tensor, out_count: torch.Tensor, workspace: torch.Tensor,
+                           insert_workspace: Optional[torch.Tensor] = None, max_rows: Optional[int] = None,
+                           stream=None):
+    """transfer_sel_ws with each destination's insert strategy honoured (rpt_bf_transfer_insert_sel_ws): a destination
+    that resolves to RPT_INSERT_PARTITIONED for max_rows takes the routed insert through insert_workspace, the
+    caller's buffer of transfer_insert_workspace_bytes(dst_filters, max_rows) bytes (None where no destination
+    routes)."""
+    if not dst_filters or len(dst_filters) != len(dst_columns):
+        raise RptError(1, "one key column per destination filter, at least one destination")
+    handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count,
+                                                      workspace)
+    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
+    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
+    darr = (KeyColumn * len(dcols))(*dcols)
+    iws_bytes = 0 if insert_workspace is None else insert_workspace.numel() * insert_workspace.element_size()
+    device, lib = filters[0].device, filters[0]._lib
+    check(lib.rpt_bf_transfer_insert_sel_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters),
+                                            sel.data_ptr(), count.data_ptr(), max_rows, out_sel.data_ptr(),
+                                            out_count.data_ptr(), workspace.data_ptr(), ws_bytes, _ptr(insert_workspace),
+                                            iws_bytes, _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,
                 validity: Optional[torch.Tensor] = None) -> KeyColumn:
     """rpt_key_column for a FLAT (key_sel None) or DICTIONARY (key_sel uint32/int32) key vector."""
@@ -349,6 +441,14 @@ class BloomFilter:
 
     def probe_strategy_for(self, n: int) -> int:
         v = self._lib.rpt_bf_probe_strategy_for(self._h, n)
+        if v < 0:
+            check(-v)
+        return v
+
+    def probe_sel_strategy_for(self, max_rows: int) -> int:
+        """The strategy this filter runs in a device-counted chain (rpt_bf_probe_sel_strategy_for): probe_strategy_for
+        with PARTITIONED and BUCKETED replaced by GATHER."""
+        v = self._lib.rpt_bf_probe_sel_strategy_for(self._h, int(max_rows))
         if v < 0:
             check(-v)
         return v
@@ -676,6 +776,10 @@ __all__: Sequence[str] = [
     "ProbeWorkspace",
     "make_column",
     "transfer_ws",
+    "probe_chain_sel_workspace_bytes",
+    "probe_chain_sel_ws",
+    "transfer_sel_ws",
+    "transfer_insert_sel_ws",
     "validity_from_mask",
     "hash_keys",
     "hash_columns",
