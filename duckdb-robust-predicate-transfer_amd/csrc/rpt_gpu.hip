@@ -54,6 +54,7 @@
 #include "kernels/insert_masked.hpp"
 #include "kernels/partition_masked.hpp"
 #include "kernels/probe_sel.hpp"
+#include "kernels/probe_sel_small.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_LDS_HYBRID_MAX_LOG
@@ -2181,6 +2182,7 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
 }
 
 #include "rpt_probe_sel.hpp"  // the device-counted probes: a chain over a selection vector with a device-side count
+#include "rpt_probe_sel_small.hpp"  // ... and their one-launch form for small batches
 
 
 int rpt_hash_combine(const rpt_key_column* col, uint64_t n, uint64_t* inout_hashes, rpt_stream_t stream) {

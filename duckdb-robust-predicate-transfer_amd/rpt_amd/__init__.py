@@ -30,6 +30,7 @@ from .bloom import (  # noqa: F401
     make_column,
     needs_resize,
     probe_chain,
+    probe_chain_sel,
     probe_chain_sel_workspace_bytes,
     probe_chain_sel_ws,
     probe_chain_workspace_bytes,
@@ -39,6 +40,7 @@ from .bloom import (  # noqa: F401
     transfer_insert_sel_ws,
     transfer_insert_workspace_bytes,
     transfer_insert_ws,
+    transfer_sel,
     transfer_sel_ws,
     transfer_ws,
     validity_from_mask,

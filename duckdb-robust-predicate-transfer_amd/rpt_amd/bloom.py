@@ -230,9 +230,9 @@ def probe_chain_sel_workspace_bytes(filters, max_rows: int) -> int:
     return int(filters[0]._lib.rpt_bf_probe_chain_sel_workspace_bytes(handles, len(filters), int(max_rows)))
 
 
-def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, workspace):
-    """The checked arguments the three device-counted calls share; every buffer is the caller's (nothing is allocated
-    here, so the calls can be captured into a graph)."""
+def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, workspace=None):
+    """The checked arguments the device-counted calls share; every buffer is the caller's (nothing is allocated here,
+    so the calls can be captured into a graph). workspace None (the one-launch calls, which take none): 0 bytes."""
     if not filters or len(filters) != len(columns):
         raise RptError(1, "one key column per filter, at least one filter")
     for name, t in (("sel", sel), ("out_sel", out_sel)):
@@ -241,7 +241,7 @@ def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, w
     for name, t in (("count", count), ("out_count", out_count)):
         if not t.is_cuda or t.element_size() != 8 or t.numel() < 1:
             raise RptError(1, f"{name} must be a 64-bit device tensor")
-    if not workspace.is_cuda or not workspace.is_contiguous():
+    if workspace is not None and (not workspace.is_cuda or not workspace.is_contiguous()):
         raise RptError(1, "workspace must be a contiguous device tensor")
     max_rows = sel.numel() if max_rows is None else int(max_rows)
     if max_rows > sel.numel() or max_rows > out_sel.numel():
@@ -249,7 +249,7 @@ def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, w
     cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
     handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
     arr = (KeyColumn * len(cols))(*cols)
-    return handles, arr, max_rows, workspace.numel() * workspace.element_size()
+    return handles, arr, max_rows, 0 if workspace is None else workspace.numel() * workspace.element_size()
 
 
 def probe_chain_sel_ws(filters, columns, sel: torch.Tensor, count: torch.Tensor, *, out_sel: torch.Tensor,
@@ -310,6 +310,37 @@ def transfer_insert_sel_ws(filters, columns, dst_filters, dst_columns, sel: torc
                                             sel.data_ptr(), count.data_ptr(), max_rows, out_sel.data_ptr(),
                                             out_count.data_ptr(), workspace.data_ptr(), ws_bytes, _ptr(insert_workspace),
                                             iws_bytes, _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def probe_chain_sel(filters, columns, sel: torch.Tensor, count: torch.Tensor, *, out_sel: torch.Tensor,
+                    out_count: torch.Tensor, max_rows: Optional[int] = None, stream=None):
+    """probe_chain_sel_ws for a small batch in one launch with no workspace (rpt_bf_probe_chain_sel): max_rows (default:
+    the length of sel) at most RPT_SMALL_PROBE_ROWS. Every filter is gathered from L2 whatever its probe strategy.
+    Arguments and result as probe_chain_sel_ws; nothing is allocated, read back or synchronized."""
+    handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count)
+    device, lib = filters[0].device, filters[0]._lib
+    check(lib.rpt_bf_probe_chain_sel(handles, arr, len(filters), sel.data_ptr(), count.data_ptr(), max_rows,
+                                     out_sel.data_ptr(), out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_sel(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, count: torch.Tensor, *,
+                 out_sel: torch.Tensor, out_count: torch.Tensor, max_rows: Optional[int] = None, stream=None):
+    """transfer_sel_ws for a small batch in one launch with no workspace (rpt_bf_transfer_sel): the chain over
+    sel[0 .. min(count, max_rows)) and the insert of its survivors into every dst_filters[j] on dst_columns[j] in the
+    same kernel; a whole backward step of predicate transfer for one vector. max_rows at most RPT_SMALL_PROBE_ROWS.
+    Arguments and result as transfer_sel_ws; nothing is allocated, read back or synchronized."""
+    if not dst_filters or len(dst_filters) != len(dst_columns):
+        raise RptError(1, "one key column per destination filter, at least one destination")
+    handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count)
+    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
+    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
+    darr = (KeyColumn * len(dcols))(*dcols)
+    device, lib = filters[0].device, filters[0]._lib
+    check(lib.rpt_bf_transfer_sel(handles, arr, len(filters), dst_handles, darr, len(dst_filters), sel.data_ptr(),
+                                  count.data_ptr(), max_rows, out_sel.data_ptr(), out_count.data_ptr(),
+                                  _stream(device, stream)), lib)
     return out_sel, out_count
 
 

@@ -414,7 +414,8 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
  *   all max_rows positions and reads every sel entry, and routing only the live prefix needs the count on the host,
  *   while a masked gather does no work past the count. Nothing switches on the survivor fraction. There is no
  *   small-batch hand-over either: max_rows does not say how many rows there are, so every size, max_rows = 1
- *   included, takes the workspace path.
+ *   included, takes the workspace path. A caller whose max_rows is at most RPT_SMALL_PROBE_ROWS has the one-launch
+ *   pair rpt_bf_probe_chain_sel / rpt_bf_transfer_sel below.
  *   Workspace: rpt_bf_probe_chain_sel_workspace_bytes(filters, n_filters, max_rows) bytes (result bits, per-segment
  *   counts and the tail's group sums and offsets for max_rows rows; no stage area, so usually far less than
  *   rpt_bf_probe_chain_workspace_bytes; 0 on null / invalid arguments), 16-byte aligned. "Caller buffers" at the top
@@ -461,6 +462,55 @@ int rpt_bf_transfer_insert_sel_ws(const rpt_bf* const* filters, const rpt_key_co
                                   const uint32_t* sel, const uint64_t* count_dev, uint64_t max_rows, uint32_t* out_sel,
                                   uint64_t* out_count_dev, void* workspace, size_t workspace_bytes,
                                   void* insert_workspace, size_t insert_workspace_bytes, rpt_stream_t stream);
+
+/* The device-counted probes for small batches: rpt_bf_probe_chain_sel_ws and rpt_bf_transfer_sel_ws in ONE launch of one
+ * workgroup, with no workspace, for max_rows <= RPT_SMALL_PROBE_ROWS: what a per-vector backward step calls (a DuckDB
+ * vector of 2048 rows, or a few of them, whose rows an earlier probe left on the device). They are to the _ws pair what
+ * rpt_bf_probe_chain is to rpt_bf_probe_chain_ws.
+ *
+ * Result: rpt_bf_probe_chain_sel_ws's / rpt_bf_transfer_sel_ws's for the same arguments. out_sel receives sel[i] for
+ *   every position i < min(*count_dev, max_rows) that passes every filters[f] on cols[f], in position order;
+ *   *out_count_dev their number; no sel entry at or past the clamped count is read, and nothing at or past the returned
+ *   count is written to out_sel (max_rows entries are enough). rpt_bf_transfer_sel: each dst_filters[j] ends
+ *   bit-identical to rpt_bf_insert of exactly those rows of dst_cols[j], ORed into what it holds, the min/max of the
+ *   selected valid I32/I64 keys folded in, a selected NULL row inserting NULL_HASH; has_data becomes 1 whenever
+ *   max_rows > 0, as for rpt_bf_transfer_sel_ws. A destination may be listed more than once (with different columns).
+ * Strategy: the kernel gathers every filter from L2, as rpt_bf_probe_chain does, and inserts with one atomic OR per
+ *   row: rpt_bf_set_probe_strategy of the probed filters and the destinations' insert strategies do not matter. It
+ *   works for any filter size.
+ * Argument checks, in rpt_bf_probe_chain_sel_ws's order and with its messages: null lists, n_filters or n_dst outside
+ *   1..RPT_MAX_CHAIN, a null handle, and a destination that is also probed (all before any handle is looked into); a
+ *   null count_dev; max_rows > RPT_SMALL_PROBE_ROWS (RPT_ERR_INVALID_ARGUMENT, "exceeds RPT_SMALL_PROBE_ROWS"; 2^32 and
+ *   more included); max_rows == 0 sets *out_count_dev to 0 (stream-ordered, on the current device: no handle is looked
+ *   into) and does nothing else; with max_rows > 0 a null sel, a null out_sel, and out_sel overlapping sel; then
+ *   filters on different devices, a bad column, a destination that is not on the chain's device. All return
+ *   RPT_ERR_INVALID_ARGUMENT before any launch.
+ * Aliasing: every thread of the kernel reads *count_dev before its first barrier and the count is written after a
+ *   later one, so out_count_dev == count_dev is allowed (the count is replaced by the survivors'). out_sel must not
+ *   overlap sel (the two ranges of max_rows entries are compared).
+ * Ordering and capture: fully stream-ordered: no synchronisation, no copy, no allocation, no workspace. Every probed
+ *   filter's deferred clear is settled first (refused inside a capture); every destination follows rpt_bf_insert's
+ *   write rules (a deferred clear or an earlier write in flight is refused inside a capture, otherwise the call is
+ *   ordered after the destination's previous write and settles its clear); all refusals come before anything is
+ *   launched. The destinations' write scopes are all held across the one launch, taken in ascending handle address
+ *   (a filter listed twice once), so threads that list the same destinations in different orders do not deadlock.
+ * When to use them (measured on an MI355X against the _ws call with the same arguments, and against the host loop
+ *   "synchronize, read the count, rpt_bf_probe_chain, one rpt_bf_insert_sel per destination"; a full vector whose sel
+ *   is ascending, 1 / 3 / 8 filters of 128 KiB or 16 MiB, 0-2 destinations, 0.1-0.9 of the rows surviving; DESIGN §5
+ *   "One launch for DuckDB-sized vectors"): at max_rows = 2048 the one-launch call is 1.2-3.9x faster per step than the
+ *   _ws call in every shape, enqueued eagerly or replayed from a graph, and 1.6-4.7x faster than the host loop. At 8192
+ *   rows it is ahead into 128 KiB filters (up to 1.57x; 4-23 % behind with one filter when 0.9 of the rows survive or two
+ *   destinations are fed) and behind into 16 MiB filters (the _ws call is up to 1.8x faster; only one filter with 0.1
+ *   surviving is ahead). At 16384 rows the _ws call is faster in every shape measured, 1.2-3.4x: one workgroup gathers
+ *   every filter word through one CU and expands the selection with 8 lanes per wave. So: one DuckDB vector per call
+ *   takes this pair; from 8192 rows on, multi-MiB filters or several destinations take the _ws pair. */
+int rpt_bf_probe_chain_sel(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                           const uint32_t* sel, const uint64_t* count_dev, uint64_t max_rows, uint32_t* out_sel,
+                           uint64_t* out_count_dev, rpt_stream_t stream);
+int rpt_bf_transfer_sel(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                        rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst, const uint32_t* sel,
+                        const uint64_t* count_dev, uint64_t max_rows, uint32_t* out_sel, uint64_t* out_count_dev,
+                        rpt_stream_t stream);
 
 /* ---- merge / fold / export ----------------------------------------------------------------- */
 /* dst |= src (same log_num_blocks, same device): merging per-thread or per-GPU partial filters

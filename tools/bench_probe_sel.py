@@ -18,6 +18,22 @@ device-event time around the second call alone. The first round warms every kern
 minimum and the maximum of the counted rounds are reported. Synthetic keys only; nothing outside the repository is read.
 Run on a GPU box:
     python tools/bench_probe_sel.py --out profiles/probe_sel/probe_sel.jsonl
+
+--small: the one-launch calls for DuckDB-sized vectors instead (rpt_bf_probe_chain_sel / rpt_bf_transfer_sel), one
+backward step of predicate transfer per vector: a full vector of max_rows positions (2048, 8192 or 16384; sel and the
+count already on the device; sel holds max_rows of the table's 2 max_rows row ids, ascending as an earlier probe leaves
+them, or in any order with --sel-order random) goes through 1, 3 or 8 filters (all 128 KiB or all 16 MiB) and its
+survivors into 0, 1 or 2 outgoing filters of the same size, about 0.1, 0.5 or 0.9 of the rows surviving the chain. Three
+ways, in one process, alternating:
+  (a) small  the one-launch call;
+  (b) ws     the workspace call it twins (rpt_bf_probe_chain_sel_ws / rpt_bf_transfer_sel_ws): 4 to 19 launches;
+  (c) loop   the host loop: synchronize, read the count, rpt_bf_probe_chain(row_sel = sel, n = count), then one
+             rpt_bf_insert_sel per outgoing filter.
+Per-step time is device-event time around `--steps` steps enqueued back to back on a warmed device, over the steps
+((c) synchronizes once per step, as it must); the median, minimum and maximum over `--reps` rounds are reported, after a
+round that is not counted. (a) and (b) are also captured into a graph of one step each and replayed `--steps` times.
+All three produce the same selection, compared after the rounds.
+    python tools/bench_probe_sel.py --small --out profiles/probe_sel_small/probe_sel_small.jsonl
 """
 import argparse
 import ctypes
@@ -134,6 +150,152 @@ def measure(n_log, kib, frac, reps, small_iters):
     return row
 
 
+# ---- --small: the one-launch calls against the workspace calls and the host loop --------------------------------------
+SMALL_ROWS = (2048, 8192, 16384)
+SMALL_CHAINS = (1, 3, 8)
+SMALL_KIB_LOG = {128: 14, 16384: 21}
+SMALL_DSTS = (0, 1, 2)
+SMALL_FRACTIONS = (0.1, 0.5, 0.9)
+SMALL_CONFIGS = [(kib, k, n, n_dst, frac) for kib in SMALL_KIB_LOG for k in SMALL_CHAINS for n in SMALL_ROWS
+                 for n_dst in SMALL_DSTS for frac in SMALL_FRACTIONS]
+
+
+class SmallPool:
+    """The filters of one size, made once: 8 probed filters over the synthetic build keys and 2 outgoing filters."""
+
+    def __init__(self, kib):
+        self.log = SMALL_KIB_LOG[kib]
+        self.n_build = 1 << (self.log + 2)
+        self.probed = []
+        for _ in range(max(SMALL_CHAINS)):
+            bf = rpt_amd.BloomFilter(log_num_blocks=self.log)
+            bf.insert(rpt_amd.synth_build_keys(self.n_build))
+            self.probed.append(bf)
+        self.dst = [rpt_amd.BloomFilter(log_num_blocks=self.log) for _ in range(max(SMALL_DSTS))]
+        for bf in self.dst:  # their first write is not the timed one
+            bf.insert(rpt_amd.synth_build_keys(1024, start=1 << 40))
+        torch.cuda.synchronize()
+
+    def close(self):
+        for bf in self.probed + self.dst:
+            bf.close()
+
+
+def measure_small(pool, kib, k, n, n_dst, frac, reps, steps, sel_order):
+    lib = rpt_amd.load()
+    filters, dsts = pool.probed[:k], pool.dst[:n_dst]
+    permille = int(round(frac ** (1.0 / k) * 1000))  # per filter, so that about `frac` survive the chain
+    # the vector's positions select n of the 2 n rows of the table's columns: in ascending order, as an earlier probe
+    # leaves its survivors, or in any order (every key load then its own cache line)
+    rows = 2 * n
+    cols = [rpt_amd.synth_probe_keys(rows, pool.n_build, permille, start=(j + 1) << 33) for j in range(k)]
+    dcols = [rpt_amd.synth_probe_keys(rows, pool.n_build, 0, start=(j + 101) << 33) for j in range(n_dst)]
+    sel = torch.randperm(rows, device="cuda")[:n]
+    if sel_order == "ascending":
+        sel = torch.sort(sel).values
+    sel = sel.to(torch.int32).contiguous()
+    count = torch.full((1,), n, dtype=torch.int64, device="cuda")
+    out = {m: (torch.empty(n, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda"))
+           for m in "abc"}
+    ws = torch.empty(max(rpt_amd.probe_chain_sel_workspace_bytes(filters, n), 256), dtype=torch.uint8, device="cuda")
+    handles = (ctypes.c_void_p * k)(*[f.handle for f in filters])
+    arr = (KeyColumn * k)(*[rpt_amd.make_column(c) for c in cols])
+    dhandles = (ctypes.c_void_p * max(n_dst, 1))(*[f.handle for f in dsts])
+    darr = (KeyColumn * max(n_dst, 1))(*[rpt_amd.make_column(c) for c in dcols])
+    p_sel, p_count = sel.data_ptr(), count.data_ptr()
+
+    def step_a(stream):
+        o, c = out["a"][0].data_ptr(), out["a"][1].data_ptr()
+        if n_dst:
+            check(lib.rpt_bf_transfer_sel(handles, arr, k, dhandles, darr, n_dst, p_sel, p_count, n, o, c, stream))
+        else:
+            check(lib.rpt_bf_probe_chain_sel(handles, arr, k, p_sel, p_count, n, o, c, stream))
+
+    def step_b(stream):
+        o, c = out["b"][0].data_ptr(), out["b"][1].data_ptr()
+        if n_dst:
+            check(lib.rpt_bf_transfer_sel_ws(handles, arr, k, dhandles, darr, n_dst, p_sel, p_count, n, o, c,
+                                             ws.data_ptr(), ws.numel(), stream))
+        else:
+            check(lib.rpt_bf_probe_chain_sel_ws(handles, arr, k, p_sel, p_count, n, o, c, ws.data_ptr(), ws.numel(),
+                                                stream))
+
+    def step_c(stream):
+        o, c = out["c"][0].data_ptr(), out["c"][1].data_ptr()
+        torch.cuda.current_stream().synchronize()
+        m = int(count.item())  # the chain takes its row count as a host argument
+        check(lib.rpt_bf_probe_chain(handles, arr, k, p_sel, m, o, c, stream))
+        for j in range(n_dst):
+            check(lib.rpt_bf_insert_sel(dsts[j].handle, ctypes.byref(darr[j]), o, c, n, stream))
+
+    def eager(step):
+        stream = torch.cuda.current_stream().cuda_stream
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            step(stream)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / steps  # us per step
+
+    def captured(step):
+        side = torch.cuda.Stream()
+        graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            step(torch.cuda.current_stream().cuda_stream)
+        return graph
+
+    def replayed(graph):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / steps
+
+    row = {"op": "probe_sel_small", "max_rows": n, "filters": k, "filter_kib": kib, "destinations": n_dst,
+           "survivor_fraction": frac, "sel_order": sel_order, "steps": steps, "reps": reps}
+    times = {name: [] for name in ("small_us", "ws_us", "loop_us", "small_graph_us", "ws_graph_us")}
+    for step in (step_a, step_b, step_c):  # every kernel once outside any capture
+        step(torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    graphs = {"small_graph_us": captured(step_a), "ws_graph_us": captured(step_b)}
+    for rep in range(reps + 1):  # the first round warms up and is not counted
+        got = {"small_us": eager(step_a), "ws_us": eager(step_b), "loop_us": eager(step_c)}
+        for name, graph in graphs.items():
+            got[name] = replayed(graph)
+        if rep:
+            for name, v in got.items():
+                times[name].append(v)
+    counts = {m: int(out[m][1].item()) for m in "abc"}
+    assert counts["a"] == counts["b"] == counts["c"], f"counts differ: {counts} {row}"
+    for m in "bc":
+        assert torch.equal(out["a"][0][: counts["a"]], out[m][0][: counts[m]]), f"selections differ: {row}"
+    row["survivors"] = counts["a"]
+    for name, v in times.items():
+        spread(name, v, row)
+    row["ws_over_small"] = round(row["ws_us_median"] / row["small_us_median"], 3)
+    row["loop_over_small"] = round(row["loop_us_median"] / row["small_us_median"], 3)
+    row["ws_graph_over_small_graph"] = round(row["ws_graph_us_median"] / row["small_graph_us_median"], 3)
+    return row
+
+
+def main_small(args, out):
+    configs = SMALL_CONFIGS if args.only is None else [SMALL_CONFIGS[args.only]]
+    pool, pool_kib = None, None
+    for kib, k, n, n_dst, frac in configs:
+        if kib != pool_kib:
+            if pool is not None:
+                pool.close()
+            pool, pool_kib = SmallPool(kib), kib
+        row = measure_small(pool, kib, k, n, n_dst, frac, max(1, args.reps), max(1, args.steps), args.sel_order)
+        print(json.dumps(row), file=out, flush=True)
+    if pool is not None:
+        pool.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=7)
@@ -141,6 +303,10 @@ def main():
     ap.add_argument("--max-row-log", type=int, default=max(ROW_LOGS), help="skip batches above 2^this rows")
     ap.add_argument("--only", type=int, default=None, help="index into the configurations (default: all)")
     ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
+    ap.add_argument("--small", action="store_true", help="the one-launch calls for DuckDB-sized vectors (see above)")
+    ap.add_argument("--steps", type=int, default=200, help="--small: steps per round")
+    ap.add_argument("--sel-order", choices=("ascending", "random"), default="ascending",
+                    help="--small: the order of the row ids in sel (an earlier probe leaves them ascending)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_probe_sel needs a GPU: nothing is measured without one")
@@ -149,6 +315,9 @@ def main():
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         out = open(args.out, "w")
+    if args.small:
+        main_small(args, out)
+        return
     configs = [c for c in CONFIGS if c[0] <= args.max_row_log]
     configs = configs if args.only is None else [configs[args.only]]
     for n_log, kib, frac in configs:
