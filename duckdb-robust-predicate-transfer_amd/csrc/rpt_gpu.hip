@@ -55,6 +55,7 @@
 #include "kernels/partition_masked.hpp"
 #include "kernels/probe_sel.hpp"
 #include "kernels/probe_sel_small.hpp"
+#include "kernels/range.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_LDS_HYBRID_MAX_LOG
@@ -1971,16 +1972,17 @@ size_t rpt_bf_probe_chain_workspace_bytes(const rpt_bf* const* filters, uint32_t
   return chain_workspace_layout(filters, n_filters, n_rows, nullptr, nullptr);
 }
 
-// The stages after the first of a workspace chain (filters[1 .. n_filters)), each ANDing its filter's result into the
-// accumulated bits ws.bits / ws.seg_counts of n rows in place. strategy[f]: filter f's resolved probe strategy.
+// The stages after the first of a workspace chain (filters[first .. n_filters)), each ANDing its filter's result into
+// the accumulated bits ws.bits / ws.seg_counts of n rows in place. strategy[f]: filter f's resolved probe strategy.
+// first = 0 (rpt_probe_range.hpp): the accumulated bits come from a range stage and filter 0 is a masked stage too.
 static int enqueue_chain_later_stages(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
                                       const int* strategy, const uint32_t* row_sel, uint64_t n, const ChainWorkspace& ws,
-                                      int device, rpt_stream_t stream) {
+                                      int device, rpt_stream_t stream, uint32_t first = 1) {
   hipStream_t s = as_stream(stream);
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   int st = RPT_OK;
   bool done = false;
-  for (uint32_t f = 1; f < n_filters; f++) {
+  for (uint32_t f = first; f < n_filters; f++) {
     const rpt_bf* bf = filters[f];
     const rpt_key_column* col = &cols[f];
     if (routed(strategy[f])) {
@@ -2183,6 +2185,7 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
 
 #include "rpt_probe_sel.hpp"  // the device-counted probes: a chain over a selection vector with a device-side count
 #include "rpt_probe_sel_small.hpp"  // ... and their one-launch form for small batches
+#include "rpt_probe_range.hpp"  // the min/max range stage: rpt_bf_range_bits and the range variants of the chain and transfers
 
 
 int rpt_hash_combine(const rpt_key_column* col, uint64_t n, uint64_t* inout_hashes, rpt_stream_t stream) {

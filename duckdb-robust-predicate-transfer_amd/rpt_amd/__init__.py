@@ -30,6 +30,8 @@ from .bloom import (  # noqa: F401
     make_column,
     needs_resize,
     probe_chain,
+    probe_chain_range_workspace_bytes,
+    probe_chain_range_ws,
     probe_chain_sel,
     probe_chain_sel_workspace_bytes,
     probe_chain_sel_ws,
@@ -39,7 +41,9 @@ from .bloom import (  # noqa: F401
     synth_probe_keys,
     transfer_insert_sel_ws,
     transfer_insert_workspace_bytes,
+    transfer_insert_range_ws,
     transfer_insert_ws,
+    transfer_range_ws,
     transfer_sel,
     transfer_sel_ws,
     transfer_ws,

@@ -137,6 +137,23 @@ SIGNATURES = {
         [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p,
          c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
     ),
+    "rpt_bf_range_bits": (c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_void_p]),
+    "rpt_bf_probe_chain_range_workspace_bytes": (c_size_t, [c_void_p, c_uint32, c_uint32, c_uint64]),
+    "rpt_bf_probe_chain_range_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t,
+         c_void_p],
+    ),
+    "rpt_bf_transfer_range_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "rpt_bf_transfer_insert_range_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
+    ),
     "rpt_bf_probe_sel_strategy_for": (c_int, [c_void_p, c_uint64]),
     "rpt_bf_probe_chain_sel_workspace_bytes": (c_size_t, [c_void_p, c_uint32, c_uint64]),
     "rpt_bf_probe_chain_sel_ws": (

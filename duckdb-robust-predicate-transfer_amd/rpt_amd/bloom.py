@@ -221,6 +221,123 @@ def transfer_insert_ws(filters, columns, dst_filters, dst_columns, *, row_sel: O
     return out_sel, out_count
 
 
+def _range_mask_of(range_mask, n_filters: int) -> int:
+    """range_mask as the C-ABI takes it: an int as it is, a sequence of bools (one per filter) as its bits."""
+    if isinstance(range_mask, (int, np.integer)) and not isinstance(range_mask, (bool, np.bool_)):
+        mask = int(range_mask)
+    else:
+        flags = list(range_mask)
+        if len(flags) != n_filters:
+            raise RptError(1, f"range_mask has {len(flags)} entries for {n_filters} filters")
+        mask = sum(1 << f for f, flag in enumerate(flags) if flag)
+    if mask < 0 or mask >= 1 << 32:
+        raise RptError(1, f"range_mask={mask} is not a 32-bit mask")
+    return mask
+
+
+def probe_chain_range_workspace_bytes(filters, range_mask, n: int) -> int:
+    """Device workspace the range calls need for these filters, this mask and n rows
+    (rpt_bf_probe_chain_range_workspace_bytes); probe_chain_workspace_bytes when the mask is 0."""
+    if not filters:
+        raise RptError(1, "at least one filter")
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    return int(filters[0]._lib.rpt_bf_probe_chain_range_workspace_bytes(
+        handles, len(filters), _range_mask_of(range_mask, len(filters)), int(n)))
+
+
+def _range_call_args(filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream):
+    """What the three range calls share: the probed columns, the mask, n, the outputs and the chain workspace
+    (allocated here when None), as probe_chain_ws prepares them."""
+    if not filters or len(filters) != len(columns):
+        raise RptError(1, "one key column per filter, at least one filter")
+    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
+    mask = _range_mask_of(range_mask, len(filters))
+    if n is None:
+        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
+        n = (row_sel.numel() if row_sel is not None else
+             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
+    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+        raise RptError(1, "row_sel must be a 32-bit device tensor")
+    device = filters[0].device
+    lib = filters[0]._lib
+    if out_sel is None:
+        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    if out_count is None:
+        out_count = torch.zeros(1, dtype=torch.int64, device=device)
+    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
+    if workspace is None:
+        need = int(lib.rpt_bf_probe_chain_range_workspace_bytes(handles, len(filters), mask, n))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            workspace.record_stream(stream)  # freed on return while the call may still run on `stream`
+    arr = (KeyColumn * len(cols))(*cols)
+    return lib, device, handles, arr, mask, n, out_sel, out_count, workspace
+
+
+def _dst_call_args(dst_filters, dst_columns):
+    if not dst_filters or len(dst_filters) != len(dst_columns):
+        raise RptError(1, "one key column per destination filter, at least one destination")
+    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
+    return (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters]), (KeyColumn * len(dcols))(*dcols)
+
+
+def probe_chain_range_ws(filters, columns, *, range_mask, row_sel: Optional[torch.Tensor] = None,
+                         n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+                         out_count: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                         stream=None) -> torch.Tensor:
+    """probe_chain_ws restricted to the rows that also lie in the min/max range of every flagged filter on its own
+    column (rpt_bf_probe_chain_range_ws). range_mask: an int (bit f flags filters[f]) or a sequence of bools, one per
+    filter. The range is read on the device when the kernels run. Workspace: probe_chain_range_workspace_bytes
+    (allocated here when None). Returns out_sel[:count] (reads the count back)."""
+    lib, device, handles, arr, mask, n, out_sel, out_count, workspace = _range_call_args(
+        filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream)
+    check(lib.rpt_bf_probe_chain_range_ws(handles, arr, len(filters), mask, _ptr(row_sel), n, out_sel.data_ptr(),
+                                          out_count.data_ptr(), workspace.data_ptr(),
+                                          workspace.numel() * workspace.element_size(), _stream(device, stream)), lib)
+    return out_sel[: int(out_count.item())]
+
+
+def transfer_range_ws(filters, columns, dst_filters, dst_columns, *, range_mask,
+                      row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                      out_sel: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None, stream=None):
+    """transfer_ws over the rows that also pass the flagged filters' range tests (rpt_bf_transfer_range_ws);
+    range_mask and workspace as in probe_chain_range_ws. Nothing is read back: returns (out_sel, out_count)."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, mask, n, out_sel, out_count, workspace = _range_call_args(
+        filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream)
+    check(lib.rpt_bf_transfer_range_ws(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
+                                       _ptr(row_sel), n, out_sel.data_ptr(), out_count.data_ptr(),
+                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                       _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_insert_range_ws(filters, columns, dst_filters, dst_columns, *, range_mask,
+                             row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                             out_sel: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None,
+                             workspace: Optional[torch.Tensor] = None,
+                             insert_workspace: Optional[torch.Tensor] = None, stream=None):
+    """transfer_insert_ws over the rows that also pass the flagged filters' range tests
+    (rpt_bf_transfer_insert_range_ws); range_mask and workspace as in probe_chain_range_ws, the insert workspace as in
+    transfer_insert_ws. Nothing is read back: returns (out_sel, out_count)."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, mask, n, out_sel, out_count, workspace = _range_call_args(
+        filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream)
+    if insert_workspace is None:
+        need = int(lib.rpt_bf_transfer_insert_workspace_bytes(dst_handles, len(dst_filters), n))
+        insert_workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            insert_workspace.record_stream(stream)
+    check(lib.rpt_bf_transfer_insert_range_ws(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
+                                              _ptr(row_sel), n, out_sel.data_ptr(), out_count.data_ptr(),
+                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                              insert_workspace.data_ptr(),
+                                              insert_workspace.numel() * insert_workspace.element_size(),
+                                              _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
 def probe_chain_sel_workspace_bytes(filters, max_rows: int) -> int:
     """Device workspace the device-counted calls need for a selection of max_rows entries
     (rpt_bf_probe_chain_sel_workspace_bytes): result bits, segment counts and the tail's sums; no stage area."""
@@ -696,6 +813,27 @@ class BloomFilter:
         col = make_column(keys, key_type, key_sel, validity)
         check(self._lib.rpt_bf_find_bits(self._h, ctypes.byref(col), n, out.data_ptr(),
                                          _stream(self.device, stream)))
+        return out
+
+    def range_bits(self, keys: torch.Tensor, *, n: Optional[int] = None, row_sel: Optional[torch.Tensor] = None,
+                   key_type: Optional[int] = None, key_sel=None, validity=None, out: Optional[torch.Tensor] = None,
+                   stream=None) -> torch.Tensor:
+        """The filter's min/max range test alone (rpt_bf_range_bits): bit i of the returned int64 words (the layout
+        of rpt_bf_probe_bits, ceil(n / 512) * 8 words) is set iff row i (or row_sel[i]) is not NULL and lies in
+        [min, max]; a filter without a value passes every row. The range is read on the device when the kernel runs.
+        `out`: a contiguous 64-bit device tensor of at least that many words (allocated here when None)."""
+        if n is None:
+            n = row_sel.numel() if row_sel is not None else (key_sel.numel() if key_sel is not None else keys.numel())
+        col = make_column(keys, key_type, key_sel, validity)
+        if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
+            raise RptError(1, "row_sel must be a 32-bit device tensor")
+        need = ((n + SEG_ROWS - 1) // SEG_ROWS) * (SEG_ROWS // 64)
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.int64, device=self.device)
+        elif not out.is_cuda or not out.is_contiguous() or out.element_size() != 8 or out.numel() < need:
+            raise RptError(1, f"out must be a contiguous device tensor of at least {need} 64-bit words")
+        check(self._lib.rpt_bf_range_bits(self._h, ctypes.byref(col), _ptr(row_sel), n, out.data_ptr(),
+                                          _stream(self.device, stream)), self._lib)
         return out
 
     # ---- merge / fold / export -------------------------------------------------------------

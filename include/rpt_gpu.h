@@ -396,6 +396,78 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
                               void* workspace, size_t workspace_bytes, void* insert_workspace,
                               size_t insert_workspace_bytes, rpt_stream_t stream);
 
+/* The min/max range stage: the other half of CREATE_BF's dynamic filter, on the device. The reference pushes a
+ * filter's Bloom test and ">= min" / "<= max" of its build keys to the probe side's scan (PushDynamicFilters,
+ * physical_create_bf.cpp:282-350; rpt_filter_type all / bf_only / minmax_only). The inserts here fold that min/max
+ * into the filter on the device (rpt_bf_get_minmax); these calls test keys against it there, reading the range from
+ * device memory when the kernel runs: no host copy of the range, no synchronisation, and a captured call sees at
+ * every replay the min/max the filter holds by then.
+ * The test, per probed row i < n (row i, or row_sel[i]) of an I64 / I32 column (I32 values sign-extended, as the
+ * inserts fold them):
+ *   the filter has a value (min <= max): the row passes iff its key is not NULL and min <= key <= max (a NULL fails,
+ *     as it fails the scan's ">= min");
+ *   it has none (no valid key was ever inserted, or rpt_bf_set_minmax(.., has_value = 0)): every row passes, NULL
+ *     rows included: the reference pushes no min/max filter then (physical_create_bf.cpp:335).
+ *
+ * rpt_bf_range_bits: the range test alone (minmax_only). out_bits has the layout of rpt_bf_probe_bits
+ *   (ceil(n/512)*8 words of device memory, bits at positions >= n are 0; nothing else is written), so it composes
+ *   with rpt_bf_insert_bits. No workspace; stream-ordered. The filter's deferred clear is settled as a probe settles
+ *   it (refused inside a capture: rpt_bf_settle first). n == 0 is a no-op; a HASH column (no key values), a null
+ *   argument or n >= 2^32 return RPT_ERR_INVALID_ARGUMENT.
+ * rpt_bf_probe_chain_range_ws, rpt_bf_transfer_range_ws, rpt_bf_transfer_insert_range_ws: rpt_bf_probe_chain_ws,
+ *   rpt_bf_transfer_ws and rpt_bf_transfer_insert_ws restricted to the rows that also pass the range test of every
+ *   flagged filter on its own column: bit f of range_mask flags filters[f] / cols[f] (all ones up to n_filters:
+ *   rpt_filter_type all). out_sel, the count, the destinations' words and min/max, has_data, and the argument,
+ *   capture and write rules follow from that; the result does not depend on the order of the filters.
+ *   range_mask == 0: each call is exactly its twin without the argument (small-batch hand-over included) and the
+ *     workspace function returns rpt_bf_probe_chain_workspace_bytes.
+ *   range_mask != 0, stage order (fixed; nothing switches on strategy or data): the flagged columns' range stages in
+ *     filter order, the first writing the accumulated result bits and per-segment counts, the others ANDing into them
+ *     in place; then every filter, filter 0 included, as a later stage of rpt_bf_probe_chain_ws (a masked GATHER / LDS
+ *     probe that skips dead 512-row segments and dead rows' gathers; or, for a PARTITIONED / BUCKETED filter, its
+ *     phase 1 over all n rows into the temporary bits, then the AND); then the selection-vector tail once; then the
+ *     inserts from the bits. Each filter's strategy is rpt_bf_probe_strategy_for(filters[f], n), as in the chain.
+ *     There is no small-batch hand-over: every n >= 1 takes the workspace path (a one-launch form is a follow-up).
+ *   Cost: the range pass reads each flagged key column once more than the plain chain does (the filter's own stage
+ *     reads the keys of the live segments again), and a routed filter 0 pays what a routed later stage pays today:
+ *     its phase 1 partitions all n rows, dead ones included, plus the AND pass.
+ *   When to use (measured, one filter, int64 ids, range call / plain call; DESIGN §5 "Min/max range stage"): the
+ *     range pass streams the whole key column at 0.95 of the box's read-stream rate, which is also about what an
+ *     LDS-sized filter's own probe costs, so in front of a cheap stage it does not pay for itself: a 128 KiB filter
+ *     takes 1.1-2.2x the plain chain's time (1.26x even when a sorted column's range covers 5 % of 2^27 rows and 95 %
+ *     of the segments die), and a routed (PARTITIONED / BUCKETED) filter, which partitions all n rows whatever is
+ *     dead, takes 1.2-1.4x. It pays in front of a stage that costs more per row than a stream: a gathered filter
+ *     (16 MiB at 2^20 rows) takes 0.71-0.77x when the range covers 5 % of the column, sorted or shuffled (dead rows
+ *     make no gather), 0.95x at 50 %, 1.04x at 100 %. Set the bit where the rows the range removes would otherwise
+ *     be gathered (or where its exact answer matters: it removes the filter's false positives outside the range
+ *     from out_sel and from the destinations); leave it clear for LDS-sized and routed filters until the range
+ *     test is fused into stage 0's key read (a follow-up). Nothing is dispatched on this: the caller chooses by
+ *     setting the mask.
+ *   Workspace: rpt_bf_probe_chain_range_workspace_bytes(filters, n_filters, range_mask, n): the chain's layout with
+ *     the temporary bits present whenever any filter routes, filter 0 included; 0 on a null / invalid argument (a
+ *     mask bit at or above n_filters among them). "Caller buffers" at the top holds: contents on entry are arbitrary,
+ *     exactly the reported size (and out_sel of exactly n entries) is enough, a misaligned workspace returns
+ *     RPT_ERR_INVALID_ARGUMENT and a too-small one RPT_ERR_WORKSPACE, both before any launch.
+ *   Arguments: a mask bit at or above n_filters, or a flagged HASH column, returns RPT_ERR_INVALID_ARGUMENT before
+ *     any launch (and before any handle is looked into); n == 0 sets the count to 0 and does nothing else.
+ *   Capture: under rpt_bf_probe_chain_ws's rules (transfers: rpt_bf_transfer_ws's). */
+int rpt_bf_range_bits(const rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
+                      uint64_t* out_bits, rpt_stream_t stream);
+size_t rpt_bf_probe_chain_range_workspace_bytes(const rpt_bf* const* filters, uint32_t n_filters, uint32_t range_mask,
+                                                uint64_t n_rows);
+int rpt_bf_probe_chain_range_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                uint32_t range_mask, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
+                                uint64_t* out_count_dev, void* workspace, size_t workspace_bytes, rpt_stream_t stream);
+int rpt_bf_transfer_range_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                             uint32_t range_mask, rpt_bf* const* dst_filters, const rpt_key_column* dst_cols,
+                             uint32_t n_dst, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
+                             uint64_t* out_count_dev, void* workspace, size_t workspace_bytes, rpt_stream_t stream);
+int rpt_bf_transfer_insert_range_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                    uint32_t range_mask, rpt_bf* const* dst_filters, const rpt_key_column* dst_cols,
+                                    uint32_t n_dst, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
+                                    uint64_t* out_count_dev, void* workspace, size_t workspace_bytes,
+                                    void* insert_workspace, size_t insert_workspace_bytes, rpt_stream_t stream);
+
 /* Device-counted probes: the survivors of an earlier probe probed again, their count never reaching the host. The
  * backward pass of predicate transfer probes the rows a table kept in the forward pass; with these calls that second
  * probe (and the insert into the filter the table sends on) is enqueued behind the first with no synchronisation.
