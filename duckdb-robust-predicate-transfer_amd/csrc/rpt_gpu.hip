@@ -713,6 +713,15 @@ int check_col(const rpt_key_column* col) {
   return RPT_OK;
 }
 
+// A caller's workspace against the bytes a call needs: null or short is RPT_ERR_WORKSPACE, misaligned
+// RPT_ERR_INVALID_ARGUMENT.
+int check_workspace(const void* workspace, size_t workspace_bytes, size_t need) {
+  if (!workspace || workspace_bytes < need)
+    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
+  return RPT_OK;
+}
+
 bool dense_ok(const rpt_key_column* col, const uint32_t* row_sel) {
   return row_sel == nullptr && col->key_sel == nullptr && (reinterpret_cast<uintptr_t>(col->keys) & 15) == 0;
 }
@@ -1420,10 +1429,8 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
     }
     return RPT_OK;
   }
-  const size_t need = insert_workspace_layout(n, L, strategy, nullptr, nullptr);
-  if (!workspace || workspace_bytes < need)
-    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
+  st = check_workspace(workspace, workspace_bytes, insert_workspace_layout(n, L, strategy, nullptr, nullptr));
+  if (st != RPT_OK) return st;
   RPT_ON_DEVICE(bf->device);
   hipStream_t s = as_stream(stream);
   RPT_REFUSE_CAPTURE_WRITE(bf, s, "insert");
@@ -1527,11 +1534,7 @@ static int check_routed_insert(const rpt_bf* bf, uint64_t n, const void* workspa
   if (!*routed) return RPT_OK;
   if (!strategy_supported(RPT_PROBE_PARTITIONED, L))
     return fail(RPT_ERR_INVALID_ARGUMENT, "partitioned insert unsupported for a 2^%d-block filter", L);
-  const size_t need = insert_workspace_layout(n, L, RPT_INSERT_PARTITIONED, nullptr, nullptr);
-  if (!workspace || workspace_bytes < need)
-    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
-  return RPT_OK;
+  return check_workspace(workspace, workspace_bytes, insert_workspace_layout(n, L, RPT_INSERT_PARTITIONED, nullptr, nullptr));
 }
 
 // enqueue_device_rows_insert's routed twin: the masked partition pass over all n rows (a row that is not selected
@@ -1632,10 +1635,8 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
   const int strategy = resolve_strategy(bf->probe_strategy.load(), L, n);
   if (!strategy_supported(strategy, L))
     return fail(RPT_ERR_INVALID_ARGUMENT, "probe strategy %d unsupported for a 2^%d-block filter", strategy, L);
-  const size_t need = workspace_layout(n, L, strategy, nullptr, nullptr);
-  if (!workspace || workspace_bytes < need)
-    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
+  st = check_workspace(workspace, workspace_bytes, workspace_layout(n, L, strategy, nullptr, nullptr));
+  if (st != RPT_OK) return st;
   RPT_ON_DEVICE(bf->device);
   ProbeWorkspace ws;
   workspace_layout(n, L, strategy, workspace, &ws);
@@ -1829,10 +1830,8 @@ int rpt_bf_probe_phase2(const rpt_bf* bf, const uint32_t* row_sel, uint64_t n, u
   if (!out_sel) return fail(RPT_ERR_INVALID_ARGUMENT, "null out_sel");
   const int L = bf->log_num_blocks;
   const int strategy = resolve_strategy(bf->probe_strategy.load(), L, n);
-  const size_t need = workspace_layout(n, L, strategy, nullptr, nullptr);
-  if (!workspace || workspace_bytes < need)
-    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
+  const int st = check_workspace(workspace, workspace_bytes, workspace_layout(n, L, strategy, nullptr, nullptr));
+  if (st != RPT_OK) return st;
   ProbeWorkspace ws;
   workspace_layout(n, L, strategy, workspace, &ws);
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
@@ -1919,16 +1918,20 @@ struct ChainWorkspace {
   size_t stage_bytes;
 };
 bool routed(int strategy) { return strategy == RPT_PROBE_PARTITIONED || strategy == RPT_PROBE_BUCKETED; }
-size_t chain_workspace_layout(const rpt_bf* const* filters, uint32_t k, uint64_t n, void* base, ChainWorkspace* ws) {
+// first_later: the first filter that runs as a later (masked) stage: 1, or 0 where range stages come before filter 0.
+// with_stages false (a device-counted chain, where no stage routes): neither of the last two parts, and no filter is
+// looked into.
+size_t chain_workspace_layout(const rpt_bf* const* filters, uint32_t k, uint64_t n, uint32_t first_later, bool with_stages,
+                              void* base, ChainWorkspace* ws) {
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
   size_t stage = 0;
   bool tmp = false;
-  for (uint32_t f = 0; f < k; f++) {
+  for (uint32_t f = 0; with_stages && f < k; f++) {
     const int L = filters[f]->log_num_blocks;
     const int st = resolve_strategy(filters[f]->probe_strategy.load(), L, n);
     stage = std::max(stage, workspace_layout(n, L, st, nullptr, nullptr));
-    tmp = tmp || (f > 0 && routed(st));
+    tmp = tmp || (f >= first_later && routed(st));
   }
   constexpr int kParts = 6;
   const size_t sz[kParts] = {align256(n_segs * rpt::kWordsPerSeg * 8), align256(n_groups * rpt::kGroupSegs * 4),
@@ -1946,7 +1949,7 @@ size_t chain_workspace_layout(const rpt_bf* const* filters, uint32_t k, uint64_t
     ws->group_sums = reinterpret_cast<uint32_t*>(p + off[2]);
     ws->group_offs = reinterpret_cast<uint32_t*>(p + off[3]);
     ws->tmp_bits = sz[4] ? reinterpret_cast<uint64_t*>(p + off[4]) : nullptr;
-    ws->stage = p + off[5];
+    ws->stage = with_stages ? p + off[5] : nullptr;
     ws->stage_bytes = sz[5];
   }
   return total;
@@ -1969,15 +1972,15 @@ size_t rpt_bf_probe_chain_workspace_bytes(const rpt_bf* const* filters, uint32_t
     fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n_rows);
     return 0;
   }
-  return chain_workspace_layout(filters, n_filters, n_rows, nullptr, nullptr);
+  return chain_workspace_layout(filters, n_filters, n_rows, 1, true, nullptr, nullptr);
 }
 
 // The stages after the first of a workspace chain (filters[first .. n_filters)), each ANDing its filter's result into
 // the accumulated bits ws.bits / ws.seg_counts of n rows in place. strategy[f]: filter f's resolved probe strategy.
-// first = 0 (rpt_probe_range.hpp): the accumulated bits come from a range stage and filter 0 is a masked stage too.
+// first = 0 (after range stages): the accumulated bits come from a range stage and filter 0 is a masked stage too.
 static int enqueue_chain_later_stages(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
                                       const int* strategy, const uint32_t* row_sel, uint64_t n, const ChainWorkspace& ws,
-                                      int device, rpt_stream_t stream, uint32_t first = 1) {
+                                      int device, rpt_stream_t stream, uint32_t first) {
   hipStream_t s = as_stream(stream);
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   int st = RPT_OK;
@@ -2016,68 +2019,6 @@ static int enqueue_chain_later_stages(const rpt_bf* const* filters, const rpt_ke
   return RPT_OK;
 }
 
-// The body of rpt_bf_probe_chain_ws, shared with rpt_bf_transfer_ws. *survivor_bits (nullable) tells the caller where
-// the survivors are once the call is enqueued: the accumulated result bits in the workspace (the workspace path), or
-// nullptr when only out_sel / *out_count_dev hold them (the small-batch hand-over) or nothing was probed (n == 0).
-static int probe_chain_ws_impl(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
-                               const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
-                               void* workspace, size_t workspace_bytes, rpt_stream_t stream,
-                               const uint64_t** survivor_bits) {
-  if (survivor_bits) *survivor_bits = nullptr;
-  if (!filters || !cols || !out_count_dev) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
-  int st = check_chain_filters(filters, n_filters);
-  if (st != RPT_OK) return st;
-  if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
-  int strategy[RPT_MAX_CHAIN];
-  bool all_auto = true;
-  for (uint32_t f = 0; f < n_filters; f++) {
-    st = check_col(&cols[f]);
-    if (st != RPT_OK) return st;
-    const int L = filters[f]->log_num_blocks, requested = filters[f]->probe_strategy.load();
-    all_auto = all_auto && requested == RPT_PROBE_AUTO;
-    strategy[f] = resolve_strategy(requested, L, n);
-    if (!strategy_supported(strategy[f], L))
-      return fail(RPT_ERR_INVALID_ARGUMENT, "probe strategy %d unsupported for a 2^%d-block filter (filter %u)", strategy[f],
-                  L, f);
-  }
-  const int device = filters[0]->device;
-  RPT_ON_DEVICE(device);
-  hipStream_t s = as_stream(stream);
-  if (n == 0) {
-    RPT_HIP(hipMemsetAsync(out_count_dev, 0, sizeof(uint64_t), s));
-    return RPT_OK;
-  }
-  if (!out_sel) return fail(RPT_ERR_INVALID_ARGUMENT, "null out_sel");
-  const size_t need = chain_workspace_layout(filters, n_filters, n, nullptr, nullptr);
-  if (!workspace || workspace_bytes < need)
-    return fail(RPT_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  if (misaligned16(workspace)) return fail(RPT_ERR_INVALID_ARGUMENT, "workspace %p is not 16-byte aligned", workspace);
-  // a DuckDB-sized batch with nothing forced: the one-launch chain kernel (the workspace stays untouched)
-  if (n <= rpt::kSmallRows && all_auto)
-    return rpt_bf_probe_chain(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, stream);
-  for (uint32_t f = 0; f < n_filters; f++) RPT_SETTLE(filters[f], s);
-  ChainWorkspace ws;
-  chain_workspace_layout(filters, n_filters, n, workspace, &ws);
-  const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
-  // stage 0: the filter's own phase 1 (the PARTITIONED one ending in result bits) into the accumulated bits and counts
-  bool done = false;
-  st = probe_phase1_impl(filters[0], &cols[0], row_sel, n, ws.stage, ws.stage_bytes, stream, nullptr, nullptr, &done,
-                         ws.bits, ws.seg_counts);
-  if (st != RPT_OK) return st;
-  st = enqueue_chain_later_stages(filters, cols, n_filters, strategy, row_sel, n, ws, device, stream);
-  if (st != RPT_OK) return st;
-  if (survivor_bits) *survivor_bits = ws.bits;
-  // the tail, once
-  return launch_sel_tail(s, ws.bits, ws.seg_counts, ws.group_sums, ws.group_offs, n_segs, row_sel, out_sel, out_count_dev);
-}
-
-int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
-                          const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
-                          void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
-  return probe_chain_ws_impl(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, workspace, workspace_bytes,
-                             stream, nullptr);
-}
-
 // A chain's survivors of n rows into the outgoing filters: from the accumulated bits (rows row_sel[i] of dst_cols[j], as
 // probed; routed[j]: the routed insert through insert_workspace), or, with bits == nullptr (after the small-batch
 // hand-over), from out_sel / *out_count_dev, which hold the same row ids.
@@ -2098,69 +2039,6 @@ static int enqueue_transfer_inserts(rpt_bf* const* dst_filters, const rpt_key_co
   return RPT_OK;
 }
 
-// The body of rpt_bf_transfer_ws and rpt_bf_transfer_insert_ws. route: a destination whose insert strategy resolves
-// to PARTITIONED for n takes the routed insert through insert_workspace (rpt_bf_transfer_insert_ws); otherwise every
-// destination takes one atomic OR per row and insert_workspace is not looked at (rpt_bf_transfer_ws).
-static int transfer_impl(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
-                         rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
-                         const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
-                         void* workspace, size_t workspace_bytes, bool route, void* insert_workspace,
-                         size_t insert_workspace_bytes, rpt_stream_t stream) {
-  if (!filters || !cols || !out_count_dev || !dst_filters || !dst_cols)
-    return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
-  if (n_filters == 0 || n_filters > RPT_MAX_CHAIN)
-    return fail(RPT_ERR_INVALID_ARGUMENT, "n_filters=%u outside 1..%d", n_filters, RPT_MAX_CHAIN);
-  if (n_dst == 0 || n_dst > RPT_MAX_CHAIN)
-    return fail(RPT_ERR_INVALID_ARGUMENT, "n_dst=%u outside 1..%d", n_dst, RPT_MAX_CHAIN);
-  // handles are compared before any of them is looked into
-  for (uint32_t f = 0; f < n_filters; f++)
-    if (!filters[f]) return fail(RPT_ERR_INVALID_ARGUMENT, "null filter %u", f);
-  for (uint32_t j = 0; j < n_dst; j++) {
-    if (!dst_filters[j]) return fail(RPT_ERR_INVALID_ARGUMENT, "null destination filter %u", j);
-    for (uint32_t f = 0; f < n_filters; f++)
-      if (dst_filters[j] == filters[f])
-        return fail(RPT_ERR_INVALID_ARGUMENT, "destination filter %u is probed filter %u of the same call", j, f);
-  }
-  int st = check_chain_filters(filters, n_filters);
-  if (st != RPT_OK) return st;
-  if (n >= (1ULL << 32)) return fail(RPT_ERR_INVALID_ARGUMENT, "n=%llu rows exceeds uint32 sel_t", (unsigned long long)n);
-  const int device = filters[0]->device;
-  for (uint32_t j = 0; j < n_dst; j++) {
-    if (dst_filters[j]->device != device)
-      return fail(RPT_ERR_INVALID_ARGUMENT, "destination filter %u is not on the chain's device", j);
-    st = check_col(&dst_cols[j]);
-    if (st != RPT_OK) return st;
-  }
-  // which destinations route, and their share of the insert workspace (they run one after another on the stream)
-  bool routed[RPT_MAX_CHAIN] = {};
-  if (route && n > 0)
-    for (uint32_t j = 0; j < n_dst; j++) {
-      st = check_routed_insert(dst_filters[j], n, insert_workspace, insert_workspace_bytes, &routed[j]);
-      if (st != RPT_OK) return st;
-    }
-  RPT_ON_DEVICE(device);
-  hipStream_t s = as_stream(stream);
-  // every destination's capture and in-flight check before the chain enqueues anything (n == 0 writes none)
-  if (n > 0)
-    for (uint32_t j = 0; j < n_dst; j++) RPT_REFUSE_CAPTURE_WRITE(dst_filters[j], s, "transfer");
-  const uint64_t* bits = nullptr;
-  st = probe_chain_ws_impl(filters, cols, n_filters, row_sel, n, out_sel, out_count_dev, workspace, workspace_bytes,
-                           stream, &bits);
-  if (st != RPT_OK || n == 0) return st;
-  // the survivors into the outgoing filters: from the accumulated bits (rows row_sel[i] of dst_cols[j], as probed),
-  // or, after the hand-over, from out_sel, which holds the same row ids
-  return enqueue_transfer_inserts(dst_filters, dst_cols, n_dst, routed, bits, row_sel, out_sel, out_count_dev, n,
-                                  insert_workspace, s);
-}
-
-int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
-                       rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
-                       const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
-                       void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
-  return transfer_impl(filters, cols, n_filters, dst_filters, dst_cols, n_dst, row_sel, n, out_sel, out_count_dev,
-                       workspace, workspace_bytes, false, nullptr, 0, stream);
-}
-
 size_t rpt_bf_transfer_insert_workspace_bytes(rpt_bf* const* dst_filters, uint32_t n_dst, uint64_t n_rows) {
   if (!dst_filters || n_dst == 0 || n_dst > RPT_MAX_CHAIN || n_rows >= (1ULL << 32)) return 0;
   size_t need = 0;
@@ -2174,13 +2052,33 @@ size_t rpt_bf_transfer_insert_workspace_bytes(rpt_bf* const* dst_filters, uint32
   return need;
 }
 
+#include "rpt_chain_call.hpp"  // ChainCall, its checks and run_chain_call: the one body of the entry points below
+
+int rpt_bf_probe_chain_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                          const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                          void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  return run_chain_call({filters, cols, n_filters, false, nullptr, nullptr, 0, false, row_sel, nullptr, n, 0, out_sel,
+                         out_count_dev, workspace, workspace_bytes, false, nullptr, 0, stream});
+}
+
+// Every destination takes one atomic OR per row; insert_workspace is not looked at.
+int rpt_bf_transfer_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                       rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                       const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                       void* workspace, size_t workspace_bytes, rpt_stream_t stream) {
+  return run_chain_call({filters, cols, n_filters, true, dst_filters, dst_cols, n_dst, false, row_sel, nullptr, n, 0,
+                         out_sel, out_count_dev, workspace, workspace_bytes, false, nullptr, 0, stream});
+}
+
+// A destination whose insert strategy resolves to PARTITIONED for n takes the routed insert through insert_workspace.
 int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
                               rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
                               const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
                               void* workspace, size_t workspace_bytes, void* insert_workspace,
                               size_t insert_workspace_bytes, rpt_stream_t stream) {
-  return transfer_impl(filters, cols, n_filters, dst_filters, dst_cols, n_dst, row_sel, n, out_sel, out_count_dev,
-                       workspace, workspace_bytes, true, insert_workspace, insert_workspace_bytes, stream);
+  return run_chain_call({filters, cols, n_filters, true, dst_filters, dst_cols, n_dst, false, row_sel, nullptr, n, 0,
+                         out_sel, out_count_dev, workspace, workspace_bytes, true, insert_workspace,
+                         insert_workspace_bytes, stream});
 }
 
 #include "rpt_probe_sel.hpp"  // the device-counted probes: a chain over a selection vector with a device-side count

@@ -50,15 +50,28 @@ def key_type_of(keys: torch.Tensor, key_type: Optional[int]) -> int:
     raise RptError(1, f"unsupported key dtype {keys.dtype}; pass key_type=RPT_KEY_HASH for hashes")
 
 
-def probe_chain(filters, columns, *, row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
-                out_sel: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None,
-                stream=None) -> torch.Tensor:
-    """USE_BF's filter chain in one launch (rpt_bf_probe_chain): ascending ids (int32) of the rows passing
-    every filters[i] on its own key column. columns[i]: a device key tensor, or a dict of make_column's
-    arguments (keys, key_type, key_sel, validity). n <= RPT_SMALL_PROBE_ROWS, 1..RPT_MAX_CHAIN filters."""
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _check_lists(filters, columns, message: str) -> None:
     if not filters or len(filters) != len(columns):
-        raise RptError(1, "one key column per filter, at least one filter")
+        raise RptError(1, message)
+
+
+def _list_args(filters, columns):
+    """(handle array, rpt_key_column array) of a filter list and its columns: device key tensors, or dicts of
+    make_column's arguments (keys, key_type, key_sel, validity)."""
     cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
+    return (ctypes.c_void_p * len(filters))(*[f._h for f in filters]), (KeyColumn * len(cols))(*cols)
+
+
+def _probed_call_args(filters, columns, row_sel, n, out_sel, out_count):
+    """The probed side of every chain and transfer call: the checked lists as arrays, n (None: the length of row_sel,
+    else of the first column's key_sel, else of its keys), the row_sel check, and out_sel / out_count (allocated here
+    when None)."""
+    _check_lists(filters, columns, "one key column per filter, at least one filter")
+    handles, arr = _list_args(filters, columns)
     if n is None:
         c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
         n = (row_sel.numel() if row_sel is not None else
@@ -70,10 +83,33 @@ def probe_chain(filters, columns, *, row_sel: Optional[torch.Tensor] = None, n: 
         out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
     if out_count is None:
         out_count = torch.zeros(1, dtype=torch.int64, device=device)
-    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
-    arr = (KeyColumn * len(cols))(*cols)
-    check(filters[0]._lib.rpt_bf_probe_chain(handles, arr, len(filters), _ptr(row_sel), n, out_sel.data_ptr(),
-                                              out_count.data_ptr(), _stream(device, stream)))
+    return filters[0]._lib, device, handles, arr, n, out_sel, out_count
+
+
+def _dst_call_args(dst_filters, dst_columns):
+    """The destination side of every transfer: the checked lists as arrays."""
+    _check_lists(dst_filters, dst_columns, "one key column per destination filter, at least one destination")
+    return _list_args(dst_filters, dst_columns)
+
+
+def _workspace_or_new(workspace: Optional[torch.Tensor], need, device, stream) -> torch.Tensor:
+    """The caller's workspace, or one of need() bytes (at least 256) allocated here."""
+    if workspace is None:
+        workspace = torch.empty(max(int(need()), 256), dtype=torch.uint8, device=device)
+        if isinstance(stream, torch.cuda.Stream):
+            workspace.record_stream(stream)  # freed on return while the call may still run on `stream`
+    return workspace
+
+
+def probe_chain(filters, columns, *, row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                out_sel: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None,
+                stream=None) -> torch.Tensor:
+    """USE_BF's filter chain in one launch (rpt_bf_probe_chain): ascending ids (int32) of the rows passing
+    every filters[i] on its own key column. columns[i]: a device key tensor, or a dict of make_column's
+    arguments (keys, key_type, key_sel, validity). n <= RPT_SMALL_PROBE_ROWS, 1..RPT_MAX_CHAIN filters."""
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    check(lib.rpt_bf_probe_chain(handles, arr, len(filters), _ptr(row_sel), n, out_sel.data_ptr(),
+                                 out_count.data_ptr(), _stream(device, stream)))
     return out_sel[: int(out_count.item())]
 
 
@@ -93,31 +129,12 @@ def probe_chain_ws(filters, columns, *, row_sel: Optional[torch.Tensor] = None, 
     bits between the filters, each filter runs its own probe strategy, and the selection vector is written once
     at the end. Arguments as probe_chain, plus a device workspace of probe_chain_workspace_bytes(filters, n) bytes
     (allocated here when None). Returns out_sel[:count] (reads the count back)."""
-    if not filters or len(filters) != len(columns):
-        raise RptError(1, "one key column per filter, at least one filter")
-    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
-    if n is None:
-        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
-        n = (row_sel.numel() if row_sel is not None else
-             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
-    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
-        raise RptError(1, "row_sel must be a 32-bit device tensor")
-    device = filters[0].device
-    lib = filters[0]._lib
-    if out_sel is None:
-        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    if out_count is None:
-        out_count = torch.zeros(1, dtype=torch.int64, device=device)
-    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
-    if workspace is None:
-        need = int(lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n))
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        if isinstance(stream, torch.cuda.Stream):
-            workspace.record_stream(stream)  # freed on return while the chain may still run on `stream`
-    arr = (KeyColumn * len(cols))(*cols)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    workspace = _workspace_or_new(
+        workspace, lambda: lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n), device, stream)
     check(lib.rpt_bf_probe_chain_ws(handles, arr, len(filters), _ptr(row_sel), n, out_sel.data_ptr(),
-                                    out_count.data_ptr(), workspace.data_ptr(),
-                                    workspace.numel() * workspace.element_size(), _stream(device, stream)), lib)
+                                    out_count.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                    _stream(device, stream)), lib)
     return out_sel[: int(out_count.item())]
 
 
@@ -130,36 +147,13 @@ def transfer_ws(filters, columns, dst_filters, dst_columns, *, row_sel: Optional
     the survivors once the stream has run). Columns as in probe_chain; the destination columns are indexed by
     the same row ids as the probed ones. A destination's is_empty() is False afterwards even if no row survived
     (set_has_data(False) restores it once a zero count has been read)."""
-    if not filters or len(filters) != len(columns):
-        raise RptError(1, "one key column per filter, at least one filter")
-    if not dst_filters or len(dst_filters) != len(dst_columns):
-        raise RptError(1, "one key column per destination filter, at least one destination")
-    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
-    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
-    if n is None:
-        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
-        n = (row_sel.numel() if row_sel is not None else
-             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
-    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
-        raise RptError(1, "row_sel must be a 32-bit device tensor")
-    device = filters[0].device
-    lib = filters[0]._lib
-    if out_sel is None:
-        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    if out_count is None:
-        out_count = torch.zeros(1, dtype=torch.int64, device=device)
-    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
-    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
-    if workspace is None:
-        need = int(lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n))
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        if isinstance(stream, torch.cuda.Stream):
-            workspace.record_stream(stream)  # freed on return while the transfer may still run on `stream`
-    arr = (KeyColumn * len(cols))(*cols)
-    darr = (KeyColumn * len(dcols))(*dcols)
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    workspace = _workspace_or_new(
+        workspace, lambda: lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n), device, stream)
     check(lib.rpt_bf_transfer_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters), _ptr(row_sel), n,
-                                 out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
-                                 workspace.numel() * workspace.element_size(), _stream(device, stream)), lib)
+                                 out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                 _stream(device, stream)), lib)
     return out_sel, out_count
 
 
@@ -181,42 +175,16 @@ def transfer_insert_ws(filters, columns, dst_filters, dst_columns, *, row_sel: O
     survivors' result bits, the others one atomic OR per row. Arguments and result as transfer_ws, plus the insert
     workspace of transfer_insert_workspace_bytes(dst_filters, n) bytes the destinations share (allocated here when
     None). Nothing is read back."""
-    if not filters or len(filters) != len(columns):
-        raise RptError(1, "one key column per filter, at least one filter")
-    if not dst_filters or len(dst_filters) != len(dst_columns):
-        raise RptError(1, "one key column per destination filter, at least one destination")
-    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
-    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
-    if n is None:
-        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
-        n = (row_sel.numel() if row_sel is not None else
-             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
-    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
-        raise RptError(1, "row_sel must be a 32-bit device tensor")
-    device = filters[0].device
-    lib = filters[0]._lib
-    if out_sel is None:
-        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    if out_count is None:
-        out_count = torch.zeros(1, dtype=torch.int64, device=device)
-    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
-    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
-    if workspace is None:
-        need = int(lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n))
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        if isinstance(stream, torch.cuda.Stream):
-            workspace.record_stream(stream)  # freed on return while the transfer may still run on `stream`
-    if insert_workspace is None:
-        need = int(lib.rpt_bf_transfer_insert_workspace_bytes(dst_handles, len(dst_filters), n))
-        insert_workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        if isinstance(stream, torch.cuda.Stream):
-            insert_workspace.record_stream(stream)
-    arr = (KeyColumn * len(cols))(*cols)
-    darr = (KeyColumn * len(dcols))(*dcols)
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    workspace = _workspace_or_new(
+        workspace, lambda: lib.rpt_bf_probe_chain_workspace_bytes(handles, len(filters), n), device, stream)
+    insert_workspace = _workspace_or_new(
+        insert_workspace, lambda: lib.rpt_bf_transfer_insert_workspace_bytes(dst_handles, len(dst_filters), n), device,
+        stream)
     check(lib.rpt_bf_transfer_insert_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters), _ptr(row_sel),
                                         n, out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
-                                        workspace.numel() * workspace.element_size(), insert_workspace.data_ptr(),
-                                        insert_workspace.numel() * insert_workspace.element_size(),
+                                        _nbytes(workspace), insert_workspace.data_ptr(), _nbytes(insert_workspace),
                                         _stream(device, stream)), lib)
     return out_sel, out_count
 
@@ -245,42 +213,6 @@ def probe_chain_range_workspace_bytes(filters, range_mask, n: int) -> int:
         handles, len(filters), _range_mask_of(range_mask, len(filters)), int(n)))
 
 
-def _range_call_args(filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream):
-    """What the three range calls share: the probed columns, the mask, n, the outputs and the chain workspace
-    (allocated here when None), as probe_chain_ws prepares them."""
-    if not filters or len(filters) != len(columns):
-        raise RptError(1, "one key column per filter, at least one filter")
-    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
-    mask = _range_mask_of(range_mask, len(filters))
-    if n is None:
-        c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
-        n = (row_sel.numel() if row_sel is not None else
-             (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
-    if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
-        raise RptError(1, "row_sel must be a 32-bit device tensor")
-    device = filters[0].device
-    lib = filters[0]._lib
-    if out_sel is None:
-        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    if out_count is None:
-        out_count = torch.zeros(1, dtype=torch.int64, device=device)
-    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
-    if workspace is None:
-        need = int(lib.rpt_bf_probe_chain_range_workspace_bytes(handles, len(filters), mask, n))
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        if isinstance(stream, torch.cuda.Stream):
-            workspace.record_stream(stream)  # freed on return while the call may still run on `stream`
-    arr = (KeyColumn * len(cols))(*cols)
-    return lib, device, handles, arr, mask, n, out_sel, out_count, workspace
-
-
-def _dst_call_args(dst_filters, dst_columns):
-    if not dst_filters or len(dst_filters) != len(dst_columns):
-        raise RptError(1, "one key column per destination filter, at least one destination")
-    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
-    return (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters]), (KeyColumn * len(dcols))(*dcols)
-
-
 def probe_chain_range_ws(filters, columns, *, range_mask, row_sel: Optional[torch.Tensor] = None,
                          n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
                          out_count: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
@@ -289,11 +221,13 @@ def probe_chain_range_ws(filters, columns, *, range_mask, row_sel: Optional[torc
     column (rpt_bf_probe_chain_range_ws). range_mask: an int (bit f flags filters[f]) or a sequence of bools, one per
     filter. The range is read on the device when the kernels run. Workspace: probe_chain_range_workspace_bytes
     (allocated here when None). Returns out_sel[:count] (reads the count back)."""
-    lib, device, handles, arr, mask, n, out_sel, out_count, workspace = _range_call_args(
-        filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    workspace = _workspace_or_new(
+        workspace, lambda: lib.rpt_bf_probe_chain_range_workspace_bytes(handles, len(filters), mask, n), device, stream)
     check(lib.rpt_bf_probe_chain_range_ws(handles, arr, len(filters), mask, _ptr(row_sel), n, out_sel.data_ptr(),
-                                          out_count.data_ptr(), workspace.data_ptr(),
-                                          workspace.numel() * workspace.element_size(), _stream(device, stream)), lib)
+                                          out_count.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                          _stream(device, stream)), lib)
     return out_sel[: int(out_count.item())]
 
 
@@ -304,12 +238,13 @@ def transfer_range_ws(filters, columns, dst_filters, dst_columns, *, range_mask,
     """transfer_ws over the rows that also pass the flagged filters' range tests (rpt_bf_transfer_range_ws);
     range_mask and workspace as in probe_chain_range_ws. Nothing is read back: returns (out_sel, out_count)."""
     dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
-    lib, device, handles, arr, mask, n, out_sel, out_count, workspace = _range_call_args(
-        filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    workspace = _workspace_or_new(
+        workspace, lambda: lib.rpt_bf_probe_chain_range_workspace_bytes(handles, len(filters), mask, n), device, stream)
     check(lib.rpt_bf_transfer_range_ws(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
                                        _ptr(row_sel), n, out_sel.data_ptr(), out_count.data_ptr(),
-                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                       _stream(device, stream)), lib)
+                                       workspace.data_ptr(), _nbytes(workspace), _stream(device, stream)), lib)
     return out_sel, out_count
 
 
@@ -322,19 +257,17 @@ def transfer_insert_range_ws(filters, columns, dst_filters, dst_columns, *, rang
     (rpt_bf_transfer_insert_range_ws); range_mask and workspace as in probe_chain_range_ws, the insert workspace as in
     transfer_insert_ws. Nothing is read back: returns (out_sel, out_count)."""
     dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
-    lib, device, handles, arr, mask, n, out_sel, out_count, workspace = _range_call_args(
-        filters, columns, range_mask, row_sel, n, out_sel, out_count, workspace, stream)
-    if insert_workspace is None:
-        need = int(lib.rpt_bf_transfer_insert_workspace_bytes(dst_handles, len(dst_filters), n))
-        insert_workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        if isinstance(stream, torch.cuda.Stream):
-            insert_workspace.record_stream(stream)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    workspace = _workspace_or_new(
+        workspace, lambda: lib.rpt_bf_probe_chain_range_workspace_bytes(handles, len(filters), mask, n), device, stream)
+    insert_workspace = _workspace_or_new(
+        insert_workspace, lambda: lib.rpt_bf_transfer_insert_workspace_bytes(dst_handles, len(dst_filters), n), device,
+        stream)
     check(lib.rpt_bf_transfer_insert_range_ws(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
                                               _ptr(row_sel), n, out_sel.data_ptr(), out_count.data_ptr(),
-                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                              insert_workspace.data_ptr(),
-                                              insert_workspace.numel() * insert_workspace.element_size(),
-                                              _stream(device, stream)), lib)
+                                              workspace.data_ptr(), _nbytes(workspace), insert_workspace.data_ptr(),
+                                              _nbytes(insert_workspace), _stream(device, stream)), lib)
     return out_sel, out_count
 
 
@@ -350,8 +283,7 @@ def probe_chain_sel_workspace_bytes(filters, max_rows: int) -> int:
 def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, workspace=None):
     """The checked arguments the device-counted calls share; every buffer is the caller's (nothing is allocated here,
     so the calls can be captured into a graph). workspace None (the one-launch calls, which take none): 0 bytes."""
-    if not filters or len(filters) != len(columns):
-        raise RptError(1, "one key column per filter, at least one filter")
+    _check_lists(filters, columns, "one key column per filter, at least one filter")
     for name, t in (("sel", sel), ("out_sel", out_sel)):
         if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4:
             raise RptError(1, f"{name} must be a contiguous 32-bit device tensor")
@@ -363,10 +295,8 @@ def _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count, w
     max_rows = sel.numel() if max_rows is None else int(max_rows)
     if max_rows > sel.numel() or max_rows > out_sel.numel():
         raise RptError(1, f"max_rows={max_rows} exceeds the entries of sel ({sel.numel()}) or out_sel ({out_sel.numel()})")
-    cols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns]
-    handles = (ctypes.c_void_p * len(filters))(*[f._h for f in filters])
-    arr = (KeyColumn * len(cols))(*cols)
-    return handles, arr, max_rows, 0 if workspace is None else workspace.numel() * workspace.element_size()
+    lib, device, handles, arr, max_rows, _, _ = _probed_call_args(filters, columns, sel, max_rows, out_sel, out_count)
+    return lib, device, handles, arr, max_rows, 0 if workspace is None else _nbytes(workspace)
 
 
 def probe_chain_sel_ws(filters, columns, sel: torch.Tensor, count: torch.Tensor, *, out_sel: torch.Tensor,
@@ -377,9 +307,8 @@ def probe_chain_sel_ws(filters, columns, sel: torch.Tensor, count: torch.Tensor,
     (default: its length). out_sel (>= max_rows entries, not overlapping sel), out_count (may be `count` itself) and
     workspace (probe_chain_sel_workspace_bytes(filters, max_rows) bytes) are the caller's. Never reads the count back
     and never synchronizes: returns the device tensors (out_sel, out_count)."""
-    handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count,
-                                                      workspace)
-    device, lib = filters[0].device, filters[0]._lib
+    lib, device, handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                   out_count, workspace)
     check(lib.rpt_bf_probe_chain_sel_ws(handles, arr, len(filters), sel.data_ptr(), count.data_ptr(), max_rows,
                                         out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(), ws_bytes,
                                         _stream(device, stream)), lib)
@@ -392,14 +321,9 @@ def transfer_sel_ws(filters, columns, dst_filters, dst_columns, sel: torch.Tenso
     """probe_chain_sel_ws, then the survivors inserted into dst_filters[j] on dst_columns[j] (rpt_bf_transfer_sel_ws):
     the backward pass of predicate transfer over a device-resident table. One atomic OR per row. Arguments and result
     as probe_chain_sel_ws; the destination columns are indexed by the same row ids as the probed ones."""
-    if not dst_filters or len(dst_filters) != len(dst_columns):
-        raise RptError(1, "one key column per destination filter, at least one destination")
-    handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count,
-                                                      workspace)
-    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
-    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
-    darr = (KeyColumn * len(dcols))(*dcols)
-    device, lib = filters[0].device, filters[0]._lib
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                   out_count, workspace)
     check(lib.rpt_bf_transfer_sel_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters), sel.data_ptr(),
                                      count.data_ptr(), max_rows, out_sel.data_ptr(), out_count.data_ptr(),
                                      workspace.data_ptr(), ws_bytes, _stream(device, stream)), lib)
@@ -414,15 +338,10 @@ def transfer_insert_sel_ws(filters, columns, dst_filters, dst_columns, sel: torc
     that resolves to RPT_INSERT_PARTITIONED for max_rows takes the routed insert through insert_workspace, the
     caller's buffer of transfer_insert_workspace_bytes(dst_filters, max_rows) bytes (None where no destination
     routes)."""
-    if not dst_filters or len(dst_filters) != len(dst_columns):
-        raise RptError(1, "one key column per destination filter, at least one destination")
-    handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count,
-                                                      workspace)
-    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
-    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
-    darr = (KeyColumn * len(dcols))(*dcols)
-    iws_bytes = 0 if insert_workspace is None else insert_workspace.numel() * insert_workspace.element_size()
-    device, lib = filters[0].device, filters[0]._lib
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                   out_count, workspace)
+    iws_bytes = 0 if insert_workspace is None else _nbytes(insert_workspace)
     check(lib.rpt_bf_transfer_insert_sel_ws(handles, arr, len(filters), dst_handles, darr, len(dst_filters),
                                             sel.data_ptr(), count.data_ptr(), max_rows, out_sel.data_ptr(),
                                             out_count.data_ptr(), workspace.data_ptr(), ws_bytes, _ptr(insert_workspace),
@@ -435,8 +354,8 @@ def probe_chain_sel(filters, columns, sel: torch.Tensor, count: torch.Tensor, *,
     """probe_chain_sel_ws for a small batch in one launch with no workspace (rpt_bf_probe_chain_sel): max_rows (default:
     the length of sel) at most RPT_SMALL_PROBE_ROWS. Every filter is gathered from L2 whatever its probe strategy.
     Arguments and result as probe_chain_sel_ws; nothing is allocated, read back or synchronized."""
-    handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count)
-    device, lib = filters[0].device, filters[0]._lib
+    lib, device, handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                    out_count)
     check(lib.rpt_bf_probe_chain_sel(handles, arr, len(filters), sel.data_ptr(), count.data_ptr(), max_rows,
                                      out_sel.data_ptr(), out_count.data_ptr(), _stream(device, stream)), lib)
     return out_sel, out_count
@@ -448,13 +367,9 @@ def transfer_sel(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, 
     sel[0 .. min(count, max_rows)) and the insert of its survivors into every dst_filters[j] on dst_columns[j] in the
     same kernel; a whole backward step of predicate transfer for one vector. max_rows at most RPT_SMALL_PROBE_ROWS.
     Arguments and result as transfer_sel_ws; nothing is allocated, read back or synchronized."""
-    if not dst_filters or len(dst_filters) != len(dst_columns):
-        raise RptError(1, "one key column per destination filter, at least one destination")
-    handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel, out_count)
-    dcols = [make_column(**c) if isinstance(c, dict) else make_column(c) for c in dst_columns]
-    dst_handles = (ctypes.c_void_p * len(dst_filters))(*[f._h for f in dst_filters])
-    darr = (KeyColumn * len(dcols))(*dcols)
-    device, lib = filters[0].device, filters[0]._lib
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                    out_count)
     check(lib.rpt_bf_transfer_sel(handles, arr, len(filters), dst_handles, darr, len(dst_filters), sel.data_ptr(),
                                   count.data_ptr(), max_rows, out_sel.data_ptr(), out_count.data_ptr(),
                                   _stream(device, stream)), lib)

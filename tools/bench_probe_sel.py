@@ -34,6 +34,7 @@ Per-step time is device-event time around `--steps` steps enqueued back to back 
 round that is not counted. (a) and (b) are also captured into a graph of one step each and replayed `--steps` times.
 All three produce the same selection, compared after the rounds.
     python tools/bench_probe_sel.py --small --out profiles/probe_sel_small/probe_sel_small.jsonl
+--rows / --fraction keep a part of them; RPT_GPU_LIB names another build of the library to measure (profiles/chain_call/).
 """
 import argparse
 import ctypes
@@ -284,6 +285,7 @@ def measure_small(pool, kib, k, n, n_dst, frac, reps, steps, sel_order):
 
 def main_small(args, out):
     configs = SMALL_CONFIGS if args.only is None else [SMALL_CONFIGS[args.only]]
+    configs = [c for c in configs if args.rows in (None, c[2]) and args.fraction in (None, c[4])]
     pool, pool_kib = None, None
     for kib, k, n, n_dst, frac in configs:
         if kib != pool_kib:
@@ -305,6 +307,8 @@ def main():
     ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
     ap.add_argument("--small", action="store_true", help="the one-launch calls for DuckDB-sized vectors (see above)")
     ap.add_argument("--steps", type=int, default=200, help="--small: steps per round")
+    ap.add_argument("--rows", type=int, default=None, help="--small: only the configurations of this many positions")
+    ap.add_argument("--fraction", type=float, default=None, help="--small: only this survivor fraction")
     ap.add_argument("--sel-order", choices=("ascending", "random"), default="ascending",
                     help="--small: the order of the row ids in sel (an earlier probe leaves them ascending)")
     args = ap.parse_args()
