@@ -1,9 +1,10 @@
 // rpt_chain_call.hpp — one description and one checked path for the chain and transfer entry points: the plain ones
 // (rpt_bf_probe_chain_ws, rpt_bf_transfer_ws, rpt_bf_transfer_insert_ws), their device-counted twins (_sel_ws; the
 // one-launch rpt_bf_probe_chain_sel / rpt_bf_transfer_sel take the checks from here and launch on their own) and their
-// range twins (_range_ws). Host code of librpt_gpu.so, included by rpt_gpu.hip inside its extern "C" block, after
+// range twins (_range_ws, _sel_range_ws; the one-launch range calls take the checks from here too). Host code of
+// librpt_gpu.so, included by rpt_gpu.hip inside its extern "C" block, after
 // chain_workspace_layout, enqueue_chain_later_stages, launch_sel_tail, check_routed_insert and
-// enqueue_transfer_inserts, and before the three headers that hold the device-counted and range stages. It launches no
+// enqueue_transfer_inserts, and before the four headers that hold the device-counted and range stages. It launches no
 // kernel itself: every launch stays in the file whose ledger records it.
 #pragma once
 
@@ -39,6 +40,7 @@ struct ChainCall {
 int enqueue_sel_stage0(const ChainCall& c, int strategy, int device, const ChainWorkspace& ws, hipStream_t s);  // rpt_probe_sel.hpp
 int check_range_mask(const ChainCall& c);                                                       // rpt_probe_range.hpp
 int enqueue_range_stages(const ChainCall& c, const ChainWorkspace& ws, hipStream_t s);         // rpt_probe_range.hpp
+int enqueue_sel_range_stages(const ChainCall& c, const ChainWorkspace& ws, hipStream_t s);     // rpt_probe_sel_range.hpp
 
 // The list checks, none of which looks into a handle: null lists, the counts, null handles, and a destination that is
 // also probed. The plain chain has no handles to compare: it leaves them to check_chain_filters, which looks at them
@@ -141,22 +143,23 @@ size_t chain_call_layout(const ChainCall& c, void* base, ChainWorkspace* ws) {
   return chain_workspace_layout(c.filters, c.n_filters, c.n, c.range_mask != 0 ? 0 : 1, !c.counted, base, ws);
 }
 
-// The body of the nine workspace calls: the checks in the family's documented order (the row-list calls, plain and
+// The body of the twelve workspace calls: the checks in the family's documented order (the row-list calls, plain and
 // range, check the destinations and refuse a captured write before they look at the probed columns, and reach the
-// workspace last; the device-counted calls check everything that needs no handle first, then the probed columns, the
-// destinations and the workspace, and only then make the device current), then stage 0, the later stages, the tail
+// workspace last; the device-counted calls, plain and range, check everything that needs no handle first, the mask
+// among it, then the probed columns, the destinations and the workspace, and only then make the device current), then
+// stage 0, the later stages, the tail
 // and the inserts. Every probed filter is settled and every destination's capture check made before anything is
 // enqueued. n == 0 / max_rows == 0 sets the count and touches nothing else.
 int run_chain_call(const ChainCall& c) {
   int st = check_chain_lists(c);
   if (st != RPT_OK) return st;
+  if (c.range_mask != 0) {  // looks into no handle: before the device-counted calls' max_rows == 0 return
+    st = check_range_mask(c);
+    if (st != RPT_OK) return st;
+  }
   if (c.counted) {
     st = check_counted_rows(c, 0xFFFFFFFFull, "uint32 sel_t");
     if (st != RPT_OK || c.n == 0) return st;
-  }
-  if (c.range_mask != 0) {
-    st = check_range_mask(c);
-    if (st != RPT_OK) return st;
   }
   st = check_chain_filters(c.filters, c.n_filters);
   if (st != RPT_OK) return st;
@@ -203,11 +206,15 @@ int run_chain_call(const ChainCall& c) {
   for (uint32_t f = 0; f < c.n_filters; f++) RPT_SETTLE(c.filters[f], s);
   ChainWorkspace ws;
   chain_call_layout(c, c.workspace, &ws);
-  // stage 0 writes every segment's words and count: the only kernel that reads *count_dev; or the flagged columns' range
+  // stage 0 writes every segment's words and count: the only kernel that reads *count_dev (filter 0's probe, or with a
+  // mask the first flagged column's range stage, the other flagged columns' following it); or the flagged columns' range
   // stages, after which filter 0 is a later stage too; or the filter's own phase 1 (the PARTITIONED one ending in result
   // bits)
   uint32_t first_later = 1;
-  if (c.counted) {
+  if (c.counted && c.range_mask != 0) {
+    st = enqueue_sel_range_stages(c, ws, s);
+    first_later = 0;
+  } else if (c.counted) {
     st = enqueue_sel_stage0(c, strategy[0], device, ws, s);
   } else if (c.range_mask != 0) {
     st = enqueue_range_stages(c, ws, s);

@@ -56,6 +56,7 @@
 #include "kernels/probe_sel.hpp"
 #include "kernels/probe_sel_small.hpp"
 #include "kernels/range.hpp"
+#include "kernels/probe_sel_range.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_LDS_HYBRID_MAX_LOG
@@ -2084,6 +2085,7 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
 #include "rpt_probe_sel.hpp"  // the device-counted probes: a chain over a selection vector with a device-side count
 #include "rpt_probe_sel_small.hpp"  // ... and their one-launch form for small batches
 #include "rpt_probe_range.hpp"  // the min/max range stage: rpt_bf_range_bits and the range variants of the chain and transfers
+#include "rpt_probe_sel_range.hpp"  // ... of the device-counted probes and of the one-launch chains
 
 
 int rpt_hash_combine(const rpt_key_column* col, uint64_t n, uint64_t* inout_hashes, rpt_stream_t stream) {

@@ -26,6 +26,27 @@ struct WriteOrders {
   }
 };
 
+// One write scope per distinct destination of a one-launch transfer (a filter listed twice is locked, waited for and
+// recorded once), taken in ascending handle address and held by `orders` across the launch; an earlier write in flight
+// is refused inside a capture and every destination's pending clear is enqueued. A chain has none.
+int take_write_orders(const ChainCall& c, hipStream_t s, WriteOrders& orders) {
+  rpt_bf* distinct[RPT_MAX_CHAIN];
+  uint32_t n_distinct = 0;
+  for (uint32_t j = 0; j < c.n_dst; j++)
+    if (std::find(distinct, distinct + n_distinct, c.dst_filters[j]) == distinct + n_distinct)
+      distinct[n_distinct++] = c.dst_filters[j];
+  std::sort(distinct, distinct + n_distinct, [](const rpt_bf* x, const rpt_bf* y) {
+    return reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y);
+  });
+  for (uint32_t i = 0; i < n_distinct; i++) orders.add(distinct[i], s);
+  for (uint32_t i = 0; i < n_distinct; i++) RPT_REFUSE_IN_FLIGHT(orders[i], "write");
+  for (uint32_t i = 0; i < n_distinct; i++) {
+    const hipError_t ez = zero_pending_locked(distinct[i], s);
+    if (ez != hipSuccess) return fail(RPT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez));
+  }
+  return RPT_OK;
+}
+
 // The body of both entry points. The checks are run_chain_call's for a device-counted call (rpt_chain_call.hpp), in
 // its order and with its messages: everything that needs no look into a handle first; max_rows == 0 then sets the
 // count and returns; then the handles are looked into. No strategy and no workspace: every filter is gathered.
@@ -66,23 +87,9 @@ int probe_chain_sel_small_impl(const ChainCall& c) {
   for (uint32_t f = 0; f < c.n_filters; f++) RPT_SETTLE(c.filters[f], s);
   // has_data becomes 1 whatever the device-side selection holds: the host cannot know it was empty
   for (uint32_t j = 0; j < c.n_dst; j++) c.dst_filters[j]->has_data.store(1);
-  // one write scope per distinct destination (a filter listed twice is locked, waited for and recorded once), taken
-  // in ascending handle address and held across the launch
-  rpt_bf* distinct[RPT_MAX_CHAIN];
-  uint32_t n_distinct = 0;
-  for (uint32_t j = 0; j < c.n_dst; j++)
-    if (std::find(distinct, distinct + n_distinct, c.dst_filters[j]) == distinct + n_distinct)
-      distinct[n_distinct++] = c.dst_filters[j];
-  std::sort(distinct, distinct + n_distinct, [](const rpt_bf* x, const rpt_bf* y) {
-    return reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y);
-  });
   WriteOrders orders;
-  for (uint32_t i = 0; i < n_distinct; i++) orders.add(distinct[i], s);
-  for (uint32_t i = 0; i < n_distinct; i++) RPT_REFUSE_IN_FLIGHT(orders[i], "write");
-  for (uint32_t i = 0; i < n_distinct; i++) {
-    const hipError_t ez = zero_pending_locked(distinct[i], s);
-    if (ez != hipSuccess) return fail(RPT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez));
-  }
+  st = take_write_orders(c, s, orders);
+  if (st != RPT_OK) return st;
   if (c.transfer) {
     ProfScope prof(inst_name<true>("probe_chain_sel_small_kernel"), s);
     hipLaunchKernelGGL(rpt::probe_chain_sel_small_kernel<true>, dim3(1), dim3(rpt::kSmallThreads), 0, s, a, d, c.sel,
@@ -94,7 +101,7 @@ int probe_chain_sel_small_impl(const ChainCall& c) {
                        c.count_dev, c.n, c.out_sel, c.out_count_dev);
     prof.end();
   }
-  for (uint32_t i = 0; i < n_distinct; i++) orders[i].done(false);
+  for (uint32_t i = 0; i < orders.n; i++) orders[i].done(false);
   RPT_LAUNCHED("probe_chain_sel_small_kernel");
   return RPT_OK;
 }

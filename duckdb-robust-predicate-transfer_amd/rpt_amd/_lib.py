@@ -179,6 +179,34 @@ SIGNATURES = {
         [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p, c_uint64,
          c_void_p, c_void_p, c_void_p],
     ),
+    "rpt_bf_probe_chain_sel_range_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+         c_size_t, c_void_p],
+    ),
+    "rpt_bf_transfer_sel_range_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p,
+         c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "rpt_bf_transfer_insert_sel_range_ws": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p,
+         c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
+    ),
+    "rpt_bf_probe_chain_sel_range": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p],
+    ),
+    "rpt_bf_transfer_sel_range": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_void_p,
+         c_uint64, c_void_p, c_void_p, c_void_p],
+    ),
+    "rpt_bf_probe_chain_range": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p],
+    ),
     "rpt_bf_probe_phase1": (
         c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_size_t, c_void_p]
     ),

@@ -376,6 +376,98 @@ def transfer_sel(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, 
     return out_sel, out_count
 
 
+def probe_chain_sel_range_ws(filters, columns, sel: torch.Tensor, count: torch.Tensor, *, range_mask,
+                             out_sel: torch.Tensor, out_count: torch.Tensor, workspace: torch.Tensor,
+                             max_rows: Optional[int] = None, stream=None):
+    """probe_chain_sel_ws restricted to the positions that also lie in the min/max range of every flagged filter on its
+    own column (rpt_bf_probe_chain_sel_range_ws). range_mask as in probe_chain_range_ws (0: probe_chain_sel_ws itself);
+    the workspace is probe_chain_sel_workspace_bytes(filters, max_rows) bytes whatever the mask. Everything else as
+    probe_chain_sel_ws."""
+    lib, device, handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                   out_count, workspace)
+    mask = _range_mask_of(range_mask, len(filters))
+    check(lib.rpt_bf_probe_chain_sel_range_ws(handles, arr, len(filters), mask, sel.data_ptr(), count.data_ptr(),
+                                              max_rows, out_sel.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
+                                              ws_bytes, _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_sel_range_ws(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, count: torch.Tensor, *,
+                          range_mask, out_sel: torch.Tensor, out_count: torch.Tensor, workspace: torch.Tensor,
+                          max_rows: Optional[int] = None, stream=None):
+    """transfer_sel_ws over the positions that also pass the flagged filters' range tests
+    (rpt_bf_transfer_sel_range_ws); range_mask and workspace as in probe_chain_sel_range_ws."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                   out_count, workspace)
+    mask = _range_mask_of(range_mask, len(filters))
+    check(lib.rpt_bf_transfer_sel_range_ws(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
+                                           sel.data_ptr(), count.data_ptr(), max_rows, out_sel.data_ptr(),
+                                           out_count.data_ptr(), workspace.data_ptr(), ws_bytes,
+                                           _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_insert_sel_range_ws(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, count: torch.Tensor, *,
+                                 range_mask, out_sel: torch.Tensor, out_count: torch.Tensor, workspace: torch.Tensor,
+                                 insert_workspace: Optional[torch.Tensor] = None, max_rows: Optional[int] = None,
+                                 stream=None):
+    """transfer_insert_sel_ws over the positions that also pass the flagged filters' range tests
+    (rpt_bf_transfer_insert_sel_range_ws); range_mask and workspace as in probe_chain_sel_range_ws, the insert
+    workspace as in transfer_insert_sel_ws."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, max_rows, ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                   out_count, workspace)
+    mask = _range_mask_of(range_mask, len(filters))
+    iws_bytes = 0 if insert_workspace is None else _nbytes(insert_workspace)
+    check(lib.rpt_bf_transfer_insert_sel_range_ws(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
+                                                  sel.data_ptr(), count.data_ptr(), max_rows, out_sel.data_ptr(),
+                                                  out_count.data_ptr(), workspace.data_ptr(), ws_bytes,
+                                                  _ptr(insert_workspace), iws_bytes, _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def probe_chain_sel_range(filters, columns, sel: torch.Tensor, count: torch.Tensor, *, range_mask,
+                          out_sel: torch.Tensor, out_count: torch.Tensor, max_rows: Optional[int] = None, stream=None):
+    """probe_chain_sel with the flagged filters' range tests, in one launch (rpt_bf_probe_chain_sel_range): a flagged
+    filter's keys are loaded once for both tests, and a row outside the range gathers no filter word. range_mask as in
+    probe_chain_range_ws (0: probe_chain_sel itself); everything else as probe_chain_sel."""
+    lib, device, handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                    out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    check(lib.rpt_bf_probe_chain_sel_range(handles, arr, len(filters), mask, sel.data_ptr(), count.data_ptr(), max_rows,
+                                           out_sel.data_ptr(), out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_sel_range(filters, columns, dst_filters, dst_columns, sel: torch.Tensor, count: torch.Tensor, *,
+                       range_mask, out_sel: torch.Tensor, out_count: torch.Tensor, max_rows: Optional[int] = None,
+                       stream=None):
+    """transfer_sel with the flagged filters' range tests, in one launch (rpt_bf_transfer_sel_range); range_mask as in
+    probe_chain_sel_range, everything else as transfer_sel."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, max_rows, _ws_bytes = _sel_call_args(filters, columns, sel, count, max_rows, out_sel,
+                                                                    out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    check(lib.rpt_bf_transfer_sel_range(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
+                                        sel.data_ptr(), count.data_ptr(), max_rows, out_sel.data_ptr(),
+                                        out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def probe_chain_range(filters, columns, *, range_mask, row_sel: Optional[torch.Tensor] = None,
+                      n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+                      out_count: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """probe_chain with the flagged filters' range tests, in one launch (rpt_bf_probe_chain_range): the result of
+    probe_chain_range_ws for n <= RPT_SMALL_PROBE_ROWS with no workspace. range_mask as in probe_chain_range_ws
+    (0: probe_chain itself). Returns out_sel[:count] (reads the count back)."""
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    check(lib.rpt_bf_probe_chain_range(handles, arr, len(filters), mask, _ptr(row_sel), n, out_sel.data_ptr(),
+                                       out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel[: int(out_count.item())]
+
+
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,
                 validity: Optional[torch.Tensor] = None) -> KeyColumn:
     """rpt_key_column for a FLAT (key_sel None) or DICTIONARY (key_sel uint32/int32) key vector."""

@@ -427,7 +427,8 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
  *     probe that skips dead 512-row segments and dead rows' gathers; or, for a PARTITIONED / BUCKETED filter, its
  *     phase 1 over all n rows into the temporary bits, then the AND); then the selection-vector tail once; then the
  *     inserts from the bits. Each filter's strategy is rpt_bf_probe_strategy_for(filters[f], n), as in the chain.
- *     There is no small-batch hand-over: every n >= 1 takes the workspace path (a one-launch form is a follow-up).
+ *     There is no small-batch hand-over: every n >= 1 takes the workspace path (the one-launch form for
+ *     n <= RPT_SMALL_PROBE_ROWS is rpt_bf_probe_chain_range below, which the caller picks).
  *   Cost: the range pass reads each flagged key column once more than the plain chain does (the filter's own stage
  *     reads the keys of the live segments again), and a routed filter 0 pays what a routed later stage pays today:
  *     its phase 1 partitions all n rows, dead ones included, plus the AND pass.
@@ -583,6 +584,92 @@ int rpt_bf_transfer_sel(const rpt_bf* const* filters, const rpt_key_column* cols
                         rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst, const uint32_t* sel,
                         const uint64_t* count_dev, uint64_t max_rows, uint32_t* out_sel, uint64_t* out_count_dev,
                         rpt_stream_t stream);
+
+/* The min/max range in the device-counted probes and in the one-launch chains: every way of calling a chain applies
+ * both halves of the dynamic filter. Each call is its twin's argument list with range_mask after n_filters (bit f flags
+ * filters[f] / cols[f], as in rpt_bf_probe_chain_range_ws), and the range test is the one described at "The min/max
+ * range stage" above, the range read from device memory when the kernel runs (a captured call sees at every replay the
+ * min/max the filter holds by then).
+ *
+ * Result. The device-counted calls return exactly rpt_bf_probe_chain_range_ws(row_sel = sel, n = min(*count_dev,
+ *   max_rows), range_mask)'s result: out_sel receives sel[i], in position order, for every position i that passes the
+ *   range test of every flagged filter on its own column and the Bloom test of every filter; *out_count_dev their
+ *   number; the transfers insert exactly those rows. rpt_bf_probe_chain_range returns rpt_bf_probe_chain_range_ws's
+ *   result for the same arguments (row_sel may be null). No result depends on the order of the filters.
+ * range_mask == 0: each call hands over to its twin without the argument (rpt_bf_probe_chain_sel_ws,
+ *   rpt_bf_transfer_sel_ws, rpt_bf_transfer_insert_sel_ws, rpt_bf_probe_chain_sel, rpt_bf_transfer_sel,
+ *   rpt_bf_probe_chain): the twin's kernels are what run and what the profiler records.
+ * Everything else is the twin's, unchanged: no sel entry at or past the clamped count is read by any kernel of the call,
+ *   nothing at or past the returned count is written to out_sel, out_count_dev == count_dev is allowed, out_sel
+ *   overlapping sel is refused, has_data, the destinations' write rules and the capture rules; in the one-launch
+ *   transfer the destinations' scopes are taken in ascending handle address and a destination may be listed twice.
+ * Arguments: the twin's checks, in its order and with its messages, plus the mask's: a bit at or above n_filters and a
+ *   flagged HASH column return RPT_ERR_INVALID_ARGUMENT. The mask is checked with the checks that look into no handle:
+ *   for the device-counted calls before max_rows == 0 sets the count and returns, so a bad mask is refused at
+ *   max_rows == 0 too, as the row-list range calls refuse it at n == 0.
+ *
+ * rpt_bf_probe_chain_sel_range_ws, rpt_bf_transfer_sel_range_ws, rpt_bf_transfer_insert_sel_range_ws (any
+ *   max_rows < 2^32). Stage order (fixed, mirroring the _range_ws calls): the first flagged filter's range stage over
+ *   sel[0 .. min(*count_dev, max_rows)), which is the only kernel of the call that reads *count_dev and writes every
+ *   512-position segment's words and count (zeros past the count); the other flagged filters' range stages, masked, over
+ *   all max_rows positions (the zero bits keep them away from sel); every filter, filter 0 included, as a masked later
+ *   stage under rpt_bf_probe_sel_strategy_for(filters[f], max_rows) (GATHER, LDS or hybrid; PARTITIONED and BUCKETED
+ *   become GATHER); the selection-vector tail once; the inserts from the bits.
+ *   Workspace: rpt_bf_probe_chain_sel_workspace_bytes(filters, n_filters, max_rows) serves the ranged calls too: no
+ *   stage routes, so the layout does not depend on the mask. Its contents on entry are arbitrary and exactly the
+ *   reported size is enough. The insert workspace is rpt_bf_transfer_insert_workspace_bytes(dst_filters, n_dst,
+ *   max_rows), as for rpt_bf_transfer_insert_sel_ws.
+ * rpt_bf_probe_chain_sel_range, rpt_bf_transfer_sel_range (max_rows <= RPT_SMALL_PROBE_ROWS) and
+ *   rpt_bf_probe_chain_range (the row-list form: row_sel / n as in rpt_bf_probe_chain, n <= RPT_SMALL_PROBE_ROWS): one
+ *   launch of one workgroup, no workspace. A (filter, 512-position segment) item of a flagged filter loads its keys
+ *   once and computes range pass and hash from that load; a row outside the range makes no filter gather. Items of
+ *   unflagged filters are the twin's. There is no one-launch row-list transfer.
+ *
+ * When to use them (measured on an MI355X, int64 keys, filter 0 flagged, its range covering 100 / 50 / 5 % of the probed
+ *   keys, about 0.9 of the rows passing each Bloom test; DESIGN §5 "Ranges in the device-counted probes"):
+ *   One launch (2048 / 8192 / 16384 positions, 1 / 3 filters of 128 KiB or 16 MiB, 0 / 1 destinations): the range test
+ *     shares the key load, so where it removes nothing (100 % cover) the ranged call takes 1.00-1.03x the plain
+ *     one-launch call's time, the only shapes in which it is slower; at 50 % cover 0.56-0.80x, at 5 % 0.32-0.65x (rows
+ *     outside the range gather no filter word and are neither written to out_sel nor inserted). Against the ranged _ws
+ *     call with the same arguments it is 1.5-4.2x faster at 2048 positions; at 8192 ahead into 128 KiB filters and, into
+ *     16 MiB filters, with one filter or a 5 % range (1.2-1.4x behind with three filters otherwise); at 16384 behind (up
+ *     to 2.7x) unless the range covers 5 % and the filters are 128 KiB or there is one of them. Against the host loop
+ *     (synchronize, read the count, rpt_bf_probe_chain_range_ws, one rpt_bf_insert_sel per destination) 2.9-7.6x faster
+ *     at 2048 positions and 1.3-4.7x at 8192. So: one DuckDB vector per call takes the one-launch calls with whatever
+ *     mask the plan asks for; the size rule is the plain pair's.
+ *   Workspace (2^20 / 2^24 rows, one filter): the range stage over a selection is a gather pass of its own, not a
+ *     stream. Where the range removes nothing it is pure cost, 1.02x (16 MiB filter, 2^20 rows) to 1.20-1.28x (128 KiB
+ *     filter) of rpt_bf_probe_chain_sel_ws; it pays once it removes rows: 0.62-0.94x at 50 % cover, 0.18-0.52x at 5 %
+ *     (part of that is the rows that are not written out). Against the host loop with rpt_bf_probe_chain_range_ws over
+ *     the survivors it takes 0.58-0.95x, except into the 16 MiB filter at 2^24 rows with half or more of the rows in
+ *     range (1.03x, 1.23x), where the host loop gets the partitioned probe. Set the bit where the range is expected to
+ *     remove rows (or where its exact answer matters); a wide range in front of an LDS-sized filter is better left clear.
+ *   Nothing is dispatched on any of this: the caller sets the mask. */
+int rpt_bf_probe_chain_sel_range_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                    uint32_t range_mask, const uint32_t* sel, const uint64_t* count_dev,
+                                    uint64_t max_rows, uint32_t* out_sel, uint64_t* out_count_dev, void* workspace,
+                                    size_t workspace_bytes, rpt_stream_t stream);
+int rpt_bf_transfer_sel_range_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                 uint32_t range_mask, rpt_bf* const* dst_filters, const rpt_key_column* dst_cols,
+                                 uint32_t n_dst, const uint32_t* sel, const uint64_t* count_dev, uint64_t max_rows,
+                                 uint32_t* out_sel, uint64_t* out_count_dev, void* workspace, size_t workspace_bytes,
+                                 rpt_stream_t stream);
+int rpt_bf_transfer_insert_sel_range_ws(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                        uint32_t range_mask, rpt_bf* const* dst_filters,
+                                        const rpt_key_column* dst_cols, uint32_t n_dst, const uint32_t* sel,
+                                        const uint64_t* count_dev, uint64_t max_rows, uint32_t* out_sel,
+                                        uint64_t* out_count_dev, void* workspace, size_t workspace_bytes,
+                                        void* insert_workspace, size_t insert_workspace_bytes, rpt_stream_t stream);
+int rpt_bf_probe_chain_sel_range(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                                 uint32_t range_mask, const uint32_t* sel, const uint64_t* count_dev, uint64_t max_rows,
+                                 uint32_t* out_sel, uint64_t* out_count_dev, rpt_stream_t stream);
+int rpt_bf_transfer_sel_range(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                              uint32_t range_mask, rpt_bf* const* dst_filters, const rpt_key_column* dst_cols,
+                              uint32_t n_dst, const uint32_t* sel, const uint64_t* count_dev, uint64_t max_rows,
+                              uint32_t* out_sel, uint64_t* out_count_dev, rpt_stream_t stream);
+int rpt_bf_probe_chain_range(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                             uint32_t range_mask, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
+                             uint64_t* out_count_dev, rpt_stream_t stream);
 
 /* ---- merge / fold / export ----------------------------------------------------------------- */
 /* dst |= src (same log_num_blocks, same device): merging per-thread or per-GPU partial filters
