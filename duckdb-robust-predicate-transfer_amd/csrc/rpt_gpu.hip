@@ -31,12 +31,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <list>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "rpt_bloom_device.hpp"
@@ -143,10 +143,11 @@ int fail(int status, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(RPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-#define RPT_LAUNCHED(name)                                                                          \
-  do {                                                                                              \
-    hipError_t e_ = hipGetLastError();                                                              \
-    if (e_ != hipSuccess) return fail(RPT_ERR_HIP, "launch of %s failed: %s", name, hipGetErrorString(e_)); \
+// A step that returns a status (a launch, an enqueue_* helper): the caller returns it unless it is RPT_OK.
+#define RPT_TRY(expr)                   \
+  do {                                  \
+    const int st_try_ = (expr);         \
+    if (st_try_ != RPT_OK) return st_try_; \
   } while (0)
 
 // Run device work on `device` and restore the caller's current device afterwards.
@@ -199,55 +200,7 @@ bool stream_capturing(hipStream_t s) {
   return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 
-// Brackets one kernel launch with events on its stream when profiling is enabled. Not on a capturing stream: an
-// event recorded there becomes a node of the graph and can never be timed (hipEventElapsedTime fails on it), so a
-// captured launch, and every replay of it, stays out of the record.
-struct ProfScope {
-  const char* name;
-  hipStream_t stream;
-  hipEvent_t start = nullptr;
-  ProfScope(const char* n, hipStream_t s) : name(n), stream(s) {
-    if (!g_prof_enabled.load(std::memory_order_relaxed) || stream_capturing(s)) return;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    start = prof_event();
-    if (start && hipEventRecord(start, stream) != hipSuccess) start = nullptr;
-  }
-  void end() {
-    if (!start) return;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    hipEvent_t e = prof_event();
-    if (e && hipEventRecord(e, stream) == hipSuccess) {
-      g_prof_pending.push_back({name, start, e});
-    } else {
-      g_prof_free.push_back(start);
-      if (e) g_prof_free.push_back(e);
-    }
-    start = nullptr;
-  }
-};
-
-// Profiling name of a kernel template instantiation, spelled as tools/pmc_summary.py short() spells
-// rocprofv3's kernel names ("partition_kernel<0,true,false,1,0>"), so bench.py can match the PMC
-// counters of exactly the instantiation that ran. Interned once per (instantiation, base name).
-template <typename T>
-std::string targ_str(T v) {
-  if constexpr (std::is_same_v<T, bool>) return v ? "true" : "false";
-  else return std::to_string(v);
-}
-template <auto... A>
-const char* inst_name(const char* base) {
-  static std::mutex mu;
-  static std::list<std::pair<const char*, std::string>> names;  // list: c_str() pointers stay valid
-  std::lock_guard<std::mutex> lk(mu);
-  for (const auto& e : names)
-    if (e.first == base) return e.second.c_str();
-  std::string s = base;
-  s += '<';
-  ((s += targ_str(A), s += ','), ...);
-  s.back() = '>';
-  names.emplace_back(base, std::move(s));
-  return names.back().second.c_str();
-}
+#include "rpt_launch.hpp"  // launch_kernel: the LDS opt-in, the profiling record, the launch and its check; dispatch_*
 
 // Has `ev` (recorded outside any capture) completed, asked while the calling thread's stream is capturing?
 // Querying an event is a potentially unsafe call under hipStreamCaptureModeGlobal (torch.cuda.graph's default)
@@ -742,212 +695,89 @@ unsigned lds_probe_grid(int device, int log_num_blocks, uint64_t n_segs) {
 }
 
 template <int K, bool D>
-void launch_probe_bits_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                         uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
-  ProfScope prof(inst_name<K, D, false, rpt::kBlockThreads>("probe_bits_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_bits_kernel<K, D, false>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts);
-  prof.end();
-}
-
-template <int K, bool D>
-void launch_probe_small_t(hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n, const uint32_t* row_sel,
-                          uint32_t* out_sel, uint64_t* out_count) {
-  ProfScope prof(inst_name<K, D>("probe_small_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_small_kernel<K, D>), dim3(1), dim3(rpt::kSmallThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, n, row_sel, out_sel, out_count);
-  prof.end();
+int launch_probe_bits_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
+                        uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
+  return launch_kernel<rpt::probe_bits_kernel<K, D, false>, K, D, false, rpt::kBlockThreads>(
+      "probe_bits_kernel", kRecorded, grid, rpt::kBlockThreads, 0, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n,
+      n_segs, bits, counts);
 }
 
 // Whole filter in LDS (dynamic LDS = filter bytes), 1024-thread workgroups (16 waves): as many per CU as
 // LDS allows. Measured against 256-thread workgroups: 16 KiB 1.79 -> 1.67 ms, 64 KiB 2.07 -> 1.73 ms per
 // 1e9 int64 keys (int32: 1.71 -> 1.26 ms); a 128 KiB filter fits one workgroup per CU either way.
-void allow_dynamic_lds(const void* fn);
 template <int K, bool D>
-void launch_probe_bits_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                             uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
-  if (bf->log_num_blocks > rpt::kLdsDirectMaxLog) {  // hybrid: the first 128 KiB in LDS, the rest from L2
-    const size_t lds = 8ULL << rpt::kLdsDirectMaxLog;
-    static std::once_flag once_h;
-    std::call_once(once_h, [] {
-      allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_hybrid_kernel<K, D>));
-    });
-    ProfScope prof(inst_name<K, D>("probe_bits_hybrid_kernel"), s);
-    hipLaunchKernelGGL((rpt::probe_bits_hybrid_kernel<K, D>), dim3(grid),
-                       dim3(rpt::kLdsProbeThreads), lds, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs,
-                       bits, counts);
-    prof.end();
-    return;
-  }
-  const size_t lds = 8ULL << bf->log_num_blocks;
-  static std::once_flag once;  // > 64 KiB of dynamic LDS must be opted into
-  std::call_once(once, [] { allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_kernel<K, D, true, rpt::kLdsProbeThreads>)); });
-  ProfScope prof(inst_name<K, D, true, rpt::kLdsProbeThreads>("probe_bits_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_bits_kernel<K, D, true, rpt::kLdsProbeThreads>), dim3(grid), dim3(rpt::kLdsProbeThreads), lds,
-                     s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts);
-  prof.end();
+int launch_probe_bits_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
+                            uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
+  if (bf->log_num_blocks > rpt::kLdsDirectMaxLog)  // hybrid: the first 128 KiB in LDS, the rest from L2
+    return launch_kernel<rpt::probe_bits_hybrid_kernel<K, D>, K, D>(
+        "probe_bits_hybrid_kernel", kRecorded | kDynamicLds, grid, rpt::kLdsProbeThreads, 8ULL << rpt::kLdsDirectMaxLog, s,
+        bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts);
+  return launch_kernel<rpt::probe_bits_kernel<K, D, true, rpt::kLdsProbeThreads>, K, D, true, rpt::kLdsProbeThreads>(
+      "probe_bits_kernel", kRecorded | kDynamicLds, grid, rpt::kLdsProbeThreads, 8ULL << bf->log_num_blocks, s, bf->words,
+      (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, counts);
 }
 
-// Let `fn` use all of the CU's 160 KiB of LDS: dynamic allowance = 160 KiB - its static LDS.
-void allow_dynamic_lds(const void* fn) {
-  hipFuncAttributes at{};
-  size_t stat = 0;
-  if (hipFuncGetAttributes(&at, fn) == hipSuccess) stat = at.sharedSizeBytes;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>((160u << 10) - stat));
-  (void)hipGetLastError();
-}
-
-// The masked twins (probe_chain.hpp) of the three direct probes, with their grids and LDS: a chain's stage i >= 1.
+// The masked twins (probe_chain.hpp) of the two LDS probes, with their LDS: a chain's stage i >= 1.
 template <int K, bool D>
-void launch_probe_bits_masked_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                                uint64_t n_segs, uint64_t* acc, uint32_t* counts) {
-  ProfScope prof(inst_name<K, D, false, rpt::kBlockThreads>("probe_bits_masked_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_bits_masked_kernel<K, D, false>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc, counts);
-  prof.end();
-}
-template <int K, bool D>
-void launch_probe_bits_masked_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                                    uint64_t n_segs, uint64_t* acc, uint32_t* counts) {
-  if (bf->log_num_blocks > rpt::kLdsDirectMaxLog) {  // hybrid: the first 128 KiB in LDS, the rest from L2
-    const size_t lds = 8ULL << rpt::kLdsDirectMaxLog;
-    static std::once_flag once_h;
-    std::call_once(once_h, [] {
-      allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_masked_hybrid_kernel<K, D>));
-    });
-    ProfScope prof(inst_name<K, D>("probe_bits_masked_hybrid_kernel"), s);
-    hipLaunchKernelGGL((rpt::probe_bits_masked_hybrid_kernel<K, D>), dim3(grid), dim3(rpt::kLdsProbeThreads), lds, s,
-                       bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc, counts);
-    prof.end();
-    return;
-  }
-  const size_t lds = 8ULL << bf->log_num_blocks;
-  static std::once_flag once;  // > 64 KiB of dynamic LDS must be opted into
-  std::call_once(once, [] {
-    allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_masked_kernel<K, D, true, rpt::kLdsProbeThreads>));
-  });
-  ProfScope prof(inst_name<K, D, true, rpt::kLdsProbeThreads>("probe_bits_masked_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_bits_masked_kernel<K, D, true, rpt::kLdsProbeThreads>), dim3(grid),
-                     dim3(rpt::kLdsProbeThreads), lds, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc,
-                     counts);
-  prof.end();
+int launch_probe_bits_masked_lds_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
+                                   uint64_t n_segs, uint64_t* acc, uint32_t* counts) {
+  if (bf->log_num_blocks > rpt::kLdsDirectMaxLog)  // hybrid: the first 128 KiB in LDS, the rest from L2
+    return launch_kernel<rpt::probe_bits_masked_hybrid_kernel<K, D>, K, D>(
+        "probe_bits_masked_hybrid_kernel", kRecorded | kDynamicLds, grid, rpt::kLdsProbeThreads,
+        8ULL << rpt::kLdsDirectMaxLog, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc, counts);
+  return launch_kernel<rpt::probe_bits_masked_kernel<K, D, true, rpt::kLdsProbeThreads>, K, D, true, rpt::kLdsProbeThreads>(
+      "probe_bits_masked_kernel", kRecorded | kDynamicLds, grid, rpt::kLdsProbeThreads, 8ULL << bf->log_num_blocks, s,
+      bf->words, (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, acc, counts);
 }
 
 template <int K, bool D, bool MM, int TM, int SP = 0>
-void launch_partition_tm(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t slice_mask,
-                         uint64_t n_tiles, uint32_t* recs, uint16_t* pos, uint32_t* runs, int64_t* stats,
-                         const uint32_t* dev_n_tiles, const uint32_t* chunk_map) {
-  if constexpr (TM == 1 && SP == 0) {
-    if (slice_mask + 1 <= 4) {  // few slices: wave-aggregated slice counters
-      launch_partition_tm<K, D, MM, 1, 4>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, chunk_map);
-      return;
-    }
-  }
-  const size_t lds = rpt::partition_lds_bytes(slice_mask + 1, TM);
-  static std::once_flag once;  // per instantiation; > 64 KiB of dynamic LDS must be opted into
-  std::call_once(once, [] { allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::partition_kernel<K, D, MM, TM, SP>)); });
-  ProfScope prof(inst_name<K, D, MM, TM, SP>("partition_kernel"), s);
-  hipLaunchKernelGGL((rpt::partition_kernel<K, D, MM, TM, SP>), dim3(grid), dim3(rpt::kTileThreads), lds, s, a, n,
-                     slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, chunk_map);
-  prof.end();
-}
-
-// Tiles of tm * kTileRows rows (rpt::tile_mult; the bucketed level 2 always passes tm = 1).
-template <int K, bool D, bool MM>
-void launch_partition_mm(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t slice_mask,
-                         uint64_t n_tiles, uint32_t* recs, uint16_t* pos, uint32_t* runs, int64_t* stats,
-                         const uint32_t* dev_n_tiles, uint32_t tm) {
-  if (tm == 2)
-    launch_partition_tm<K, D, MM, 2>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, nullptr);
-  else
-    launch_partition_tm<K, D, MM, 1>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, nullptr);
-}
-
-// stats == nullptr: probe (no min/max); otherwise the build's key min/max is folded into stats.
-template <int K, bool D>
-void launch_partition_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t slice_mask,
+int launch_partition_tm(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t slice_mask,
                         uint64_t n_tiles, uint32_t* recs, uint16_t* pos, uint32_t* runs, int64_t* stats,
-                        const uint32_t* dev_n_tiles, uint32_t tm) {
-  if (rpt::KeyTraits<K>::kValues && stats != nullptr)
-    launch_partition_mm<K, D, true>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, tm);
-  else
-    launch_partition_mm<K, D, false>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, nullptr, dev_n_tiles, tm);
+                        const uint32_t* dev_n_tiles, const uint32_t* chunk_map) {
+  if constexpr (TM == 1 && SP == 0) {
+    if (slice_mask + 1 <= 4)  // few slices: wave-aggregated slice counters
+      return launch_partition_tm<K, D, MM, 1, 4>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles,
+                                                 chunk_map);
+  }
+  return launch_kernel<rpt::partition_kernel<K, D, MM, TM, SP>, K, D, MM, TM, SP>(
+      "partition_kernel", kRecorded | kDynamicLds, grid, rpt::kTileThreads, rpt::partition_lds_bytes(slice_mask + 1, TM), s,
+      a, n, slice_mask, n_tiles, recs, pos, runs, stats, dev_n_tiles, chunk_map);
+}
+
+// Tiles of tm * kTileRows rows (rpt::tile_mult). stats == nullptr: probe (no min/max); otherwise the build's key
+// min/max is folded into stats.
+template <int K, bool D>
+int launch_partition_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t slice_mask,
+                       uint64_t n_tiles, uint32_t* recs, uint16_t* pos, uint32_t* runs, int64_t* stats,
+                       const uint32_t* dev_n_tiles, uint32_t tm) {
+  return dispatch_bool(rpt::KeyTraits<K>::kValues && stats != nullptr, [&](auto mm) {
+    return dispatch_tm(tm, [&](auto t) {
+      return launch_partition_tm<K, D, mm(), t()>(grid, s, a, n, slice_mask, n_tiles, recs, pos, runs,
+                                                  mm() ? stats : nullptr, dev_n_tiles, nullptr);
+    });
+  });
 }
 
 // Level 2 of the bucketed strategies: the partition over the level-2 hash array, tile t = chunks
-// chunk_map[4t ..] (bucketed.hpp).
-void launch_partition_level2(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint64_t n_tiles,
-                             uint32_t* recs, uint16_t* pos, uint32_t* runs, const uint32_t* dev_n_tiles,
-                             const uint32_t* chunk_map) {
-  launch_partition_tm<rpt::kKeySplit, true, false, 1>(grid, s, a, n, rpt::kBucketSlices - 1, n_tiles, recs, pos, runs,
-                                                      nullptr, dev_n_tiles, chunk_map);
+// chunk_map[4t ..] (bucketed.hpp), always with tm = 1.
+int launch_partition_level2(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint64_t n_tiles,
+                            uint32_t* recs, uint16_t* pos, uint32_t* runs, const uint32_t* dev_n_tiles,
+                            const uint32_t* chunk_map) {
+  return launch_partition_tm<rpt::kKeySplit, true, false, 1>(grid, s, a, n, rpt::kBucketSlices - 1, n_tiles, recs, pos, runs,
+                                                             nullptr, dev_n_tiles, chunk_map);
 }
 
 template <int K, bool D>
-void launch_insert_t(unsigned grid, hipStream_t s, rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n, uint64_t n_segs) {
-  ProfScope prof(inst_name<K, D>("insert_kernel"), s);
-  hipLaunchKernelGGL((rpt::insert_kernel<K, D>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bf->stats);
-  prof.end();
-}
-
-// The inserts whose rows are chosen on the device (insert_masked.hpp).
-template <int K, bool D>
-void launch_insert_bits_t(unsigned grid, hipStream_t s, rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n, uint64_t n_segs,
-                          const uint64_t* bits) {
-  ProfScope prof(inst_name<K, D>("insert_bits_kernel"), s);
-  hipLaunchKernelGGL((rpt::insert_bits_kernel<K, D>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bits, bf->stats);
-  prof.end();
-}
-template <int K, bool D>  // D unused: a selection vector is always the general mapping
-void launch_insert_sel_t(unsigned grid, hipStream_t s, rpt_bf* bf, const rpt::KeyArgs& a, const uint64_t* count_dev,
-                         uint64_t max_rows) {
-  ProfScope prof(inst_name<K>("insert_sel_kernel"), s);
-  hipLaunchKernelGGL((rpt::insert_sel_kernel<K>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->words,
-                     (1ULL << bf->log_num_blocks) - 1, a, count_dev, max_rows, bf->stats);
-  prof.end();
-}
-
-template <int K, bool D>
-void launch_bucket_scatter_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t bucket_mask,
-                             const rpt::L1Lists& lists, uint32_t* hash_lo, uint8_t* hash_hi, uint16_t* pos1,
-                             uint32_t* counts_tm, uint32_t* pre_tm, int64_t* stats) {
+int launch_bucket_scatter_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a, uint64_t n, uint32_t bucket_mask,
+                            const rpt::L1Lists& lists, uint32_t* hash_lo, uint8_t* hash_hi, uint16_t* pos1,
+                            uint32_t* counts_tm, uint32_t* pre_tm, int64_t* stats) {
   const size_t lds = rpt::kL1TileRows * 8;  // the tile's hashes
-  if (rpt::KeyTraits<K>::kValues && stats != nullptr) {
-    static std::once_flag once;  // > 64 KiB of dynamic LDS must be opted into (160 KiB minus the static part)
-    std::call_once(once, [] { allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::bucket_scatter_kernel<K, D, true>)); });
-    ProfScope prof(inst_name<K, D, true>("bucket_scatter_kernel"), s);
-    hipLaunchKernelGGL((rpt::bucket_scatter_kernel<K, D, true>), dim3(grid), dim3(rpt::kTileThreads), lds, s, a, n,
-                       bucket_mask, lists, hash_lo, hash_hi, pos1, counts_tm, pre_tm, stats);
-    prof.end();
-  } else {
-    static std::once_flag once;
-    std::call_once(once, [] { allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::bucket_scatter_kernel<K, D, false>)); });
-    ProfScope prof(inst_name<K, D, false>("bucket_scatter_kernel"), s);
-    hipLaunchKernelGGL((rpt::bucket_scatter_kernel<K, D, false>), dim3(grid), dim3(rpt::kTileThreads), lds, s, a, n,
-                       bucket_mask, lists, hash_lo, hash_hi, pos1, counts_tm, pre_tm, static_cast<int64_t*>(nullptr));
-    prof.end();
-  }
+  return dispatch_bool(rpt::KeyTraits<K>::kValues && stats != nullptr, [&](auto mm) {
+    return launch_kernel<rpt::bucket_scatter_kernel<K, D, mm()>, K, D, mm()>(
+        "bucket_scatter_kernel", kRecorded | kDynamicLds, grid, rpt::kTileThreads, lds, s, a, n, bucket_mask, lists, hash_lo,
+        hash_hi, pos1, counts_tm, pre_tm, mm() ? stats : nullptr);
+  });
 }
-
-#define RPT_DISPATCH_KD(fn, kt, dense, ...)                  \
-  do {                                                       \
-    switch (kt) {                                            \
-      case RPT_KEY_I64:                                      \
-        if (dense) fn<rpt::kKeyI64, true>(__VA_ARGS__);      \
-        else fn<rpt::kKeyI64, false>(__VA_ARGS__);           \
-        break;                                               \
-      case RPT_KEY_I32:                                      \
-        if (dense) fn<rpt::kKeyI32, true>(__VA_ARGS__);      \
-        else fn<rpt::kKeyI32, false>(__VA_ARGS__);           \
-        break;                                               \
-      default:                                               \
-        if (dense) fn<rpt::kKeyHash, true>(__VA_ARGS__);     \
-        else fn<rpt::kKeyHash, false>(__VA_ARGS__);          \
-        break;                                               \
-    }                                                        \
-  } while (0)
 
 #include "rpt_routed_insert.hpp"  // the masked partition pass of the routed device-side inserts
 
@@ -955,12 +785,9 @@ void launch_bucket_scatter_t(unsigned grid, hipStream_t s, const rpt::KeyArgs& a
 int transpose_u32(hipStream_t s, const uint32_t* in, uint64_t rows, uint64_t cols, uint32_t* out, uint32_t* heavy = nullptr,
                   uint32_t heavy_run = 0, uint32_t epoch = 0) {
   if (ceil_div(cols, 64) > 65535) return fail(RPT_ERR_INVALID_ARGUMENT, "transpose of %llu columns", (unsigned long long)cols);
-  ProfScope prof_t("runs_transpose_kernel", s);
-  hipLaunchKernelGGL(rpt::runs_transpose_kernel, dim3(static_cast<unsigned>(ceil_div(rows, 64)), static_cast<unsigned>(ceil_div(cols, 64))),
-                     dim3(rpt::kBlockThreads), 0, s, in, static_cast<uint32_t>(cols), rows, out, heavy, heavy_run, epoch);
-  prof_t.end();
-  RPT_LAUNCHED("runs_transpose_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::runs_transpose_kernel>(
+      "runs_transpose_kernel", kRecorded, dim3(static_cast<unsigned>(ceil_div(rows, 64)), static_cast<unsigned>(ceil_div(cols, 64))),
+      rpt::kBlockThreads, 0, s, in, static_cast<uint32_t>(cols), rows, out, heavy, heavy_run, epoch);
 }
 
 // Level 1 of the bucketed strategies (bucketed.hpp): one pass over the keys appends every row's hash to
@@ -999,15 +826,12 @@ int run_bucket_level1(hipStream_t s, int key_type, const rpt::KeyArgs& a, bool d
 #ifdef RPT_TESTING_HOOKS
   if (g_force_l1_error.load()) lists.k_fixed = lists.n_ext = 0;  // every chunk past the bound: the error path
 #endif
-  RPT_DISPATCH_KD(launch_bucket_scatter_t, key_type, dense, static_cast<unsigned>(g.t1), s, a, n, g.nb - 1, lists, w.hash_lo,
-                  w.hash_hi, w.pos1, w.counts_tm, w.pre_tm, stats);
-  RPT_LAUNCHED("bucket_scatter_kernel");
-  ProfScope prof("bucket_lists_kernel", s);
-  hipLaunchKernelGGL(rpt::bucket_lists_kernel, dim3(g.nb), dim3(rpt::kListsThreads), 0, s, lists, g.nb, w.chunk_map,
-                     w.list_base, w.bucket_tiles, w.hash_lo, w.hash_hi);
-  prof.end();
-  RPT_LAUNCHED("bucket_lists_kernel");
-  return RPT_OK;
+  RPT_TRY(dispatch_kd(key_type, dense, [&](auto k, auto d) {
+    return launch_bucket_scatter_t<k(), d()>(static_cast<unsigned>(g.t1), s, a, n, g.nb - 1, lists, w.hash_lo, w.hash_hi,
+                                             w.pos1, w.counts_tm, w.pre_tm, stats);
+  }));
+  return launch_kernel<rpt::bucket_lists_kernel>("bucket_lists_kernel", kRecorded, g.nb, rpt::kListsThreads, 0, s, lists,
+                                                 g.nb, w.chunk_map, w.list_base, w.bucket_tiles, w.hash_lo, w.hash_hi);
 }
 
 int alloc_words(rpt_bf* bf, int log_nb) {
@@ -1067,28 +891,10 @@ int launch_hash(const rpt_key_column* col, uint64_t n, uint64_t* out_hashes, rpt
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(ceil_div(n, rpt::kBlockThreads), 4096));
   const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, nullptr};
   hipStream_t s = as_stream(stream);
-  switch (col->key_type) {
-    case RPT_KEY_I64: {
-      ProfScope prof_(inst_name<rpt::kKeyI64, COMBINE>("hash_kernel"), s);
-      hipLaunchKernelGGL((rpt::hash_kernel<rpt::kKeyI64, COMBINE>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, a, n, out_hashes);
-      prof_.end();
-      break;
-    }
-    case RPT_KEY_I32: {
-      ProfScope prof_(inst_name<rpt::kKeyI32, COMBINE>("hash_kernel"), s);
-      hipLaunchKernelGGL((rpt::hash_kernel<rpt::kKeyI32, COMBINE>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, a, n, out_hashes);
-      prof_.end();
-      break;
-    }
-    default: {
-      ProfScope prof_(inst_name<rpt::kKeyHash, COMBINE>("hash_kernel"), s);
-      hipLaunchKernelGGL((rpt::hash_kernel<rpt::kKeyHash, COMBINE>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, a, n, out_hashes);
-      prof_.end();
-      break;
-    }
-  }
-  RPT_LAUNCHED("hash_kernel");
-  return RPT_OK;
+  return dispatch_k(col->key_type, [&](auto k) {
+    return launch_kernel<rpt::hash_kernel<k(), COMBINE>, k(), COMBINE>("hash_kernel", kRecorded, grid, rpt::kBlockThreads, 0,
+                                                                      s, a, n, out_hashes);
+  });
 }
 }  // namespace
 
@@ -1253,9 +1059,9 @@ int rpt_bf_clear(rpt_bf* bf, rpt_stream_t stream) {
   // the words are zeroed by the next operation on them (rpt_bf::clear_pending): a slice insert that
   // stores every slice whole needs no separate pass over the filter (8 GiB C5 filter: 1.35 ms)
   bf->clear_pending.store(true);
-  hipLaunchKernelGGL(stats_reset_kernel, dim3(1), dim3(1), 0, as_stream(stream), bf->stats);
+  const int st = launch_kernel<stats_reset_kernel>("stats_reset_kernel", kUnrecorded, 1, 1, 0, as_stream(stream), bf->stats);
   order.done(true);
-  RPT_LAUNCHED("stats_reset_kernel");
+  if (st != RPT_OK) return st;
   bf->has_data.store(0);
   return RPT_OK;
 }
@@ -1313,10 +1119,13 @@ int rpt_bf_insert(rpt_bf* bf, const rpt_key_column* col, uint64_t n, rpt_stream_
   RPT_REFUSE_IN_FLIGHT(order, "write");
   const hipError_t ez = zero_pending_locked(bf, as_stream(stream));
   if (ez != hipSuccess) return fail(RPT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez));
-  RPT_DISPATCH_KD(launch_insert_t, col->key_type, dense_ok(col, nullptr), grid, as_stream(stream), bf, a, n, n_segs);
+  st = dispatch_kd(col->key_type, dense_ok(col, nullptr), [&](auto k, auto d) {
+    return launch_kernel<rpt::insert_kernel<k(), d()>, k(), d()>("insert_kernel", kRecorded, grid, rpt::kBlockThreads, 0,
+                                                               as_stream(stream), bf->words,
+                                                               (1ULL << bf->log_num_blocks) - 1, a, n, n_segs, bf->stats);
+  });
   order.done(false);
-  RPT_LAUNCHED("insert_kernel");
-  return RPT_OK;
+  return st;
 }
 
 // The write scope of rpt_bf_insert around an insert whose rows are chosen on the device (insert_masked.hpp):
@@ -1333,13 +1142,20 @@ static int enqueue_device_rows_insert(rpt_bf* bf, const rpt_key_column* col, con
   RPT_REFUSE_IN_FLIGHT(order, "write");
   const hipError_t ez = zero_pending_locked(bf, s);
   if (ez != hipSuccess) return fail(RPT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez));
+  const uint64_t block_mask = (1ULL << bf->log_num_blocks) - 1;
+  int st;
   if (bits != nullptr)
-    RPT_DISPATCH_KD(launch_insert_bits_t, col->key_type, dense_ok(col, sel), grid, s, bf, a, n, n_segs, bits);
-  else
-    RPT_DISPATCH_KD(launch_insert_sel_t, col->key_type, false, grid, s, bf, a, count_dev, n);
+    st = dispatch_kd(col->key_type, dense_ok(col, sel), [&](auto k, auto d) {
+      return launch_kernel<rpt::insert_bits_kernel<k(), d()>, k(), d()>(
+          "insert_bits_kernel", kRecorded, grid, rpt::kBlockThreads, 0, s, bf->words, block_mask, a, n, n_segs, bits, bf->stats);
+    });
+  else  // a selection vector is always the general mapping
+    st = dispatch_k(col->key_type, [&](auto k) {
+      return launch_kernel<rpt::insert_sel_kernel<k()>, k()>("insert_sel_kernel", kRecorded, grid, rpt::kBlockThreads, 0, s,
+                                                           bf->words, block_mask, a, count_dev, n, bf->stats);
+    });
   order.done(false);
-  RPT_LAUNCHED(bits != nullptr ? "insert_bits_kernel" : "insert_sel_kernel");
-  return RPT_OK;
+  return st;
 }
 
 int rpt_bf_insert_bits(rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n,
@@ -1471,12 +1287,14 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
     grid_slices = bucket_count(L) * rpt::kBucketSlices;
   }
   if (buck)
-    launch_partition_level2(static_cast<unsigned>(n_tiles), s, pa, n_part, n_tiles, ws.recs, nullptr, ws.runs_tm, dev_n_tiles,
-                            ws.chunk_map);
+    st = launch_partition_level2(static_cast<unsigned>(n_tiles), s, pa, n_part, n_tiles, ws.recs, nullptr, ws.runs_tm,
+                                 dev_n_tiles, ws.chunk_map);
   else
-    RPT_DISPATCH_KD(launch_partition_t, col->key_type, dense, static_cast<unsigned>(n_tiles), s, pa, n_part, tile_slices - 1,
-                    n_tiles, ws.recs, static_cast<uint16_t*>(nullptr), ws.runs_tm, bf->stats, dev_n_tiles, tm);
-  RPT_LAUNCHED("partition_kernel");
+    st = dispatch_kd(col->key_type, dense, [&](auto k, auto d) {
+      return launch_partition_t<k(), d()>(static_cast<unsigned>(n_tiles), s, pa, n_part, tile_slices - 1, n_tiles, ws.recs,
+                                          nullptr, ws.runs_tm, bf->stats, dev_n_tiles, tm);
+    });
+  if (st != RPT_OK) return st;
   return finish_routed_insert(bf, s, captured, ws, n_tiles, tile_slices, tm, grid_slices, bucket_tiles,
                               buck ? l1_error_flag(ws.lists, l1_geom(n, L)) : nullptr);
 }
@@ -1489,7 +1307,7 @@ int rpt_bf_insert_ws(rpt_bf* bf, const rpt_key_column* col, uint64_t n, void* wo
 static int finish_routed_insert(rpt_bf* bf, hipStream_t s, bool captured, const InsertWorkspace& ws, uint64_t n_tiles,
                                 uint32_t tile_slices, uint32_t tm, uint32_t grid_slices, const uint32_t* bucket_tiles,
                                 const uint32_t* l1_error) {
-  const int st = transpose_u32(s, ws.runs_tm, n_tiles, tile_slices, ws.runs);
+  int st = transpose_u32(s, ws.runs_tm, n_tiles, tile_slices, ws.runs);
   if (st != RPT_OK) return st;
   const uint32_t splits = static_cast<uint32_t>(std::max<uint64_t>(
       1, std::min<uint64_t>(n_tiles, static_cast<uint64_t>(num_cus(bf->device)) / grid_slices)));
@@ -1508,21 +1326,19 @@ static int finish_routed_insert(rpt_bf* bf, hipStream_t s, bool captured, const 
   const int mode = store_all ? rpt::kSliceMergeStoreAll
                    : (splits > 1 || captured) ? rpt::kSliceMergeAtomic
                                 : (bf->pristine ? rpt::kSliceMergeStore : rpt::kSliceMergeAdaptive);
-  ProfScope prof_i("slice_insert_kernel", s);
-  hipLaunchKernelGGL(rpt::slice_insert_kernel, dim3(grid_slices * splits), dim3(rpt::kSliceThreads), 0, s, bf->words, splits,
-                     n_tiles, ws.recs, ws.runs, static_cast<uint32_t>(rpt::tile_cap_for(tile_slices, tm)), bucket_tiles, mode);
-  prof_i.end();
-  if (l1_error != nullptr) {  // a level-1 bound hit (never expected): every bit set instead of keys missing
+  st = launch_kernel<rpt::slice_insert_kernel>("slice_insert_kernel", kRecorded, grid_slices * splits, rpt::kSliceThreads, 0, s,
+                                               bf->words, splits, n_tiles, ws.recs, ws.runs,
+                                               static_cast<uint32_t>(rpt::tile_cap_for(tile_slices, tm)), bucket_tiles, mode);
+  if (st == RPT_OK && l1_error != nullptr) {  // a level-1 bound hit (never expected): every bit set instead of keys missing
     const uint64_t n_words = 1ULL << bf->log_num_blocks;
-    hipLaunchKernelGGL(rpt::l1_error_fill_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(ceil_div(n_words, rpt::kErrorFillThreads * 8ULL), 4096))),
-                       dim3(rpt::kErrorFillThreads), 0, s, bf->words, n_words, l1_error);
+    st = launch_kernel<rpt::l1_error_fill_kernel>(
+        "l1_error_fill_kernel", kUnrecorded,
+        static_cast<unsigned>(std::min<uint64_t>(ceil_div(n_words, rpt::kErrorFillThreads * 8ULL), 4096)),
+        rpt::kErrorFillThreads, 0, s, bf->words, n_words, l1_error);
   }
-  const hipError_t el = hipGetLastError();
-  if (store_all && el == hipSuccess) bf->clear_pending.store(false);  // the slice stores zeroed the words
+  if (store_all && st == RPT_OK) bf->clear_pending.store(false);  // the slice stores zeroed the words
   order.done(false);
-  if (el != hipSuccess) return fail(RPT_ERR_HIP, "slice_insert_kernel launch: %s", hipGetErrorString(el));
-  RPT_LAUNCHED("slice_insert_kernel");
-  return RPT_OK;
+  return st;
 }
 
 // ---- routed device-side inserts (kernels/partition_masked.hpp) ------------------------------------------------
@@ -1556,13 +1372,8 @@ static int enqueue_routed_rows_insert(rpt_bf* bf, const rpt_key_column* col, con
   const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, sel};
   const uint32_t slices = slice_count(L), tm = tile_mult_of(slices);
   const uint64_t n_tiles = ceil_div(n, rpt::kTileRows * tm);
-  if (bits != nullptr)
-    RPT_DISPATCH_KD(launch_partition_bits_t, col->key_type, dense_ok(col, sel), static_cast<unsigned>(n_tiles), s, a, n,
-                    slices - 1, ws.recs, ws.runs_tm, bf->stats, bits, tm);
-  else
-    RPT_DISPATCH_KD(launch_partition_sel_t, col->key_type, false, static_cast<unsigned>(n_tiles), s, a, n, slices - 1,
-                    ws.recs, ws.runs_tm, bf->stats, count_dev, tm);
-  RPT_LAUNCHED("partition_masked_kernel");
+  RPT_TRY(launch_partition_masked(col->key_type, dense_ok(col, sel), static_cast<unsigned>(n_tiles), s, a, n, slices - 1,
+                                  ws.recs, ws.runs_tm, bf->stats, bits, count_dev, tm));
   return finish_routed_insert(bf, s, captured, ws, n_tiles, slices, tm, slices, nullptr, nullptr);
 }
 
@@ -1613,10 +1424,9 @@ int rpt_bf_find_bits(const rpt_bf* bf, const rpt_key_column* col, uint64_t n, ui
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   const unsigned grid = persistent_grid(bf->device, n_segs);
   const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, nullptr};
-  RPT_DISPATCH_KD(launch_probe_bits_t, col->key_type, dense_ok(col, nullptr), grid, as_stream(stream), bf, a, n,
-                  n_segs, out_bits, static_cast<uint32_t*>(nullptr));
-  RPT_LAUNCHED("probe_bits_kernel");
-  return RPT_OK;
+  return dispatch_kd(col->key_type, dense_ok(col, nullptr), [&](auto k, auto d) {
+    return launch_probe_bits_t<k(), d()>(grid, as_stream(stream), bf, a, n, n_segs, out_bits, nullptr);
+  });
 }
 
 
@@ -1650,12 +1460,14 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
   const bool dense = dense_ok(col, row_sel);
   if (strategy == RPT_PROBE_GATHER) {
     const unsigned grid = persistent_grid(bf->device, n_segs);
-    RPT_DISPATCH_KD(launch_probe_bits_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
-    RPT_LAUNCHED("probe_bits_kernel");
+    return dispatch_kd(col->key_type, dense, [&](auto k, auto d) {
+      return launch_probe_bits_t<k(), d()>(grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
+    });
   } else if (strategy == RPT_PROBE_LDS) {
     const unsigned grid = lds_probe_grid(bf->device, L, n_segs);
-    RPT_DISPATCH_KD(launch_probe_bits_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
-    RPT_LAUNCHED("probe_bits_kernel<lds>");
+    return dispatch_kd(col->key_type, dense, [&](auto k, auto d) {
+      return launch_probe_bits_lds_t<k(), d()>(grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
+    });
   } else {
     // PARTITIONED: the key column, tiles of slice_count(L) slices. BUCKETED: level 1 first, then the
     // same pipeline over the level-2 hash array (tiles of 256 slices, bucket by bucket), then level 1's
@@ -1686,12 +1498,14 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
     }
     const int cus = num_cus(bf->device);
     if (buck)
-      launch_partition_level2(static_cast<unsigned>(n_tiles), s, pa, n_part, n_tiles, ws.recs, ws.pos, ws.runs_tm, dev_n_tiles,
-                              ws.chunk_map);
+      st = launch_partition_level2(static_cast<unsigned>(n_tiles), s, pa, n_part, n_tiles, ws.recs, ws.pos, ws.runs_tm,
+                                   dev_n_tiles, ws.chunk_map);
     else
-      RPT_DISPATCH_KD(launch_partition_t, col->key_type, dense, static_cast<unsigned>(n_tiles), s, pa, n_part, tile_slices - 1,
-                      n_tiles, ws.recs, ws.pos, ws.runs_tm, static_cast<int64_t*>(nullptr), dev_n_tiles, tm);
-    RPT_LAUNCHED("partition_kernel");
+      st = dispatch_kd(col->key_type, dense, [&](auto k, auto d) {
+        return launch_partition_t<k(), d()>(static_cast<unsigned>(n_tiles), s, pa, n_part, tile_slices - 1, n_tiles, ws.recs,
+                                            ws.pos, ws.runs_tm, nullptr, dev_n_tiles, tm);
+      });
+    if (st != RPT_OK) return st;
     // skewed probe keys: slices whose run in some tile is over 4x the mean get mult x finer work items
     rpt::SkewItems skew;
     const bool skewed = !buck && RPT_SLICE_SKEW_MULT > 1 && tile_slices >= 16 && ws.heavy != nullptr;
@@ -1719,12 +1533,10 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
         std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, resident / grid_slices)));
     skew.base = grid_slices * splits;
     const uint32_t n_items = skew.base * (skewed ? 1 + skew.mult : 1);
-    ProfScope prof6_("slice_probe_kernel", s);
-    hipLaunchKernelGGL(rpt::slice_probe_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(skew.base, resident))),
-                       dim3(rpt::kSliceThreads), 0, s, bf->words, splits, n_tiles, ws.recs, ws.runs, ws.passb,
-                       static_cast<uint32_t>(rpt::tile_cap_for(tile_slices, tm)), bucket_tiles, n_items, skew);
-    prof6_.end();
-    RPT_LAUNCHED("slice_probe_kernel");
+    RPT_TRY(launch_kernel<rpt::slice_probe_kernel>(
+        "slice_probe_kernel", kRecorded, static_cast<unsigned>(std::min<uint64_t>(skew.base, resident)), rpt::kSliceThreads, 0,
+        s, bf->words, splits, n_tiles, ws.recs, ws.runs, ws.passb, static_cast<uint32_t>(rpt::tile_cap_for(tile_slices, tm)),
+        bucket_tiles, n_items, skew));
     const uint64_t cap = rpt::tile_cap_for(tile_slices, tm);
     if (!buck && out_sel != nullptr && out_count_dev != nullptr) {
       // tile survivor counts (in seg_counts; then their prefix inside blocks of 256 tiles) -> block sums and
@@ -1733,50 +1545,31 @@ static int probe_phase1_impl(const rpt_bf* bf, const rpt_key_column* col, const 
       const uint64_t n_blocks = ceil_div(n_tiles, rpt::kTileBlock);
       uint32_t* block_sums = reinterpret_cast<uint32_t*>(ws.bits);
       uint32_t* block_offs = block_sums + n_blocks;
-      ProfScope prof7a_("tile_count_kernel", s);
-      hipLaunchKernelGGL(rpt::tile_count_kernel, dim3(static_cast<unsigned>(ceil_div(n_tiles, rpt::kTileCountThreads / 64))),
-                         dim3(rpt::kTileCountThreads), 0, s, ws.passb, ws.runs_tm, tile_slices, n_tiles, cap, tile_counts);
-      prof7a_.end();
-      RPT_LAUNCHED("tile_count_kernel");
-      ProfScope prof7b_("tile_block_scan_kernel", s);
-      hipLaunchKernelGGL(rpt::tile_block_scan_kernel, dim3(static_cast<unsigned>(n_blocks)), dim3(rpt::kTileBlock), 0, s,
-                         tile_counts, n_tiles, block_sums);
-      prof7b_.end();
-      ProfScope prof7d_("group_scan_kernel", s);
-      hipLaunchKernelGGL(rpt::group_scan_kernel, dim3(1), dim3(1024), 0, s, block_sums, static_cast<uint32_t>(n_blocks),
-                         block_offs, out_count_dev);
-      prof7d_.end();
-      RPT_LAUNCHED("group_scan_kernel");
-      ProfScope prof7c_(tm == 2 ? "unpermute_sel_kernel<2>" : "unpermute_sel_kernel<1>", s);
-      if (tm == 2)
-        hipLaunchKernelGGL(rpt::unpermute_sel_kernel<2>, dim3(static_cast<unsigned>(n_tiles)), dim3(rpt::kUnpermuteSelThreads<2>),
-                           0, s, ws.pos, ws.passb, n, cap, tile_counts, block_offs, row_sel, out_sel);
-      else
-        hipLaunchKernelGGL(rpt::unpermute_sel_kernel<1>, dim3(static_cast<unsigned>(n_tiles)), dim3(rpt::kUnpermuteSelThreads<1>),
-                           0, s, ws.pos, ws.passb, n, cap, tile_counts, block_offs, row_sel, out_sel);
-      prof7c_.end();
-      RPT_LAUNCHED("unpermute_sel_kernel");
+      RPT_TRY(launch_kernel<rpt::tile_count_kernel>(
+          "tile_count_kernel", kRecorded, static_cast<unsigned>(ceil_div(n_tiles, rpt::kTileCountThreads / 64)),
+          rpt::kTileCountThreads, 0, s, ws.passb, ws.runs_tm, tile_slices, n_tiles, cap, tile_counts));
+      RPT_TRY(launch_kernel<rpt::tile_block_scan_kernel>("tile_block_scan_kernel", kRecorded, static_cast<unsigned>(n_blocks),
+                                                         rpt::kTileBlock, 0, s, tile_counts, n_tiles, block_sums));
+      RPT_TRY(launch_kernel<rpt::group_scan_kernel>("group_scan_kernel", kRecorded, 1, 1024, 0, s, block_sums,
+                                                    static_cast<uint32_t>(n_blocks), block_offs, out_count_dev));
+      RPT_TRY(dispatch_tm(tm, [&](auto t) {
+        return launch_kernel<rpt::unpermute_sel_kernel<t()>, t()>(
+            "unpermute_sel_kernel", kRecorded, static_cast<unsigned>(n_tiles), rpt::kUnpermuteSelThreads<t()>, 0, s, ws.pos,
+            ws.passb, n, cap, tile_counts, block_offs, row_sel, out_sel);
+      }));
       *done = true;
       return RPT_OK;
     }
-    ProfScope prof7_(tm == 2 ? "unpermute_kernel<2>" : "unpermute_kernel<1>", s);
-    if (tm == 2)
-      hipLaunchKernelGGL(rpt::unpermute_kernel<2>, dim3(static_cast<unsigned>(n_tiles)), dim3(rpt::kUnpermuteThreads), 0,
-                         s, ws.pos, ws.passb, n_part, cap, part_bits, part_counts, dev_n_tiles);
-    else
-      hipLaunchKernelGGL(rpt::unpermute_kernel<1>, dim3(static_cast<unsigned>(n_tiles)), dim3(rpt::kUnpermuteThreads), 0,
-                         s, ws.pos, ws.passb, n_part, cap, part_bits, part_counts, dev_n_tiles);
-    prof7_.end();
-    RPT_LAUNCHED("unpermute_kernel");
-    if (buck) {
-      ProfScope prof8b_("bucket_unpermute_kernel", s);
-      hipLaunchKernelGGL(rpt::bucket_unpermute_kernel, dim3(static_cast<unsigned>(ceil_div(n, rpt::kL1TileRows))),
-                         dim3(rpt::kBucketUnpermuteThreads), 0, s, ws.pos1, ws.bits2, n, bucket_count(L) - 1,
-                         ws.counts_tm, ws.pre_tm, ws.list_base, l1_geom(n, L).groups, l1_error_flag(ws.lists, l1_geom(n, L)),
-                         ws.bits, ws.seg_counts);
-      prof8b_.end();
-      RPT_LAUNCHED("bucket_unpermute_kernel");
-    }
+    RPT_TRY(dispatch_tm(tm, [&](auto t) {
+      return launch_kernel<rpt::unpermute_kernel<t()>, t()>("unpermute_kernel", kRecorded, static_cast<unsigned>(n_tiles),
+                                                            rpt::kUnpermuteThreads, 0, s, ws.pos, ws.passb, n_part, cap,
+                                                            part_bits, part_counts, dev_n_tiles);
+    }));
+    if (buck)
+      return launch_kernel<rpt::bucket_unpermute_kernel>(
+          "bucket_unpermute_kernel", kRecorded, static_cast<unsigned>(ceil_div(n, rpt::kL1TileRows)),
+          rpt::kBucketUnpermuteThreads, 0, s, ws.pos1, ws.bits2, n, bucket_count(L) - 1, ws.counts_tm, ws.pre_tm, ws.list_base,
+          l1_geom(n, L).groups, l1_error_flag(ws.lists, l1_geom(n, L)), ws.bits, ws.seg_counts);
   }
   return RPT_OK;
 }
@@ -1800,22 +1593,12 @@ static int launch_sel_tail(hipStream_t s, const uint64_t* bits, const uint32_t* 
                            uint32_t* group_offs, uint64_t n_segs, const uint32_t* row_sel, uint32_t* out_sel,
                            uint64_t* out_count_dev) {
   const uint64_t n_groups = ceil_div(n_segs, rpt::kGroupSegs);
-  ProfScope prof8_("group_sum_kernel", s);
-  hipLaunchKernelGGL(rpt::group_sum_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s,
-                     seg_counts, n_segs, group_sums);
-  prof8_.end();
-  RPT_LAUNCHED("group_sum_kernel");
-  ProfScope prof9_("group_scan_kernel", s);
-  hipLaunchKernelGGL(rpt::group_scan_kernel, dim3(1), dim3(1024), 0, s, group_sums, static_cast<uint32_t>(n_groups),
-                     group_offs, out_count_dev);
-  prof9_.end();
-  RPT_LAUNCHED("group_scan_kernel");
-  ProfScope prof10_("compact_kernel", s);
-  hipLaunchKernelGGL(rpt::compact_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(rpt::kBlockThreads), 0, s, bits,
-                     seg_counts, n_segs, group_offs, row_sel, out_sel);
-  prof10_.end();
-  RPT_LAUNCHED("compact_kernel");
-  return RPT_OK;
+  RPT_TRY(launch_kernel<rpt::group_sum_kernel>("group_sum_kernel", kRecorded, static_cast<unsigned>(n_groups),
+                                               rpt::kBlockThreads, 0, s, seg_counts, n_segs, group_sums));
+  RPT_TRY(launch_kernel<rpt::group_scan_kernel>("group_scan_kernel", kRecorded, 1, 1024, 0, s, group_sums,
+                                                static_cast<uint32_t>(n_groups), group_offs, out_count_dev));
+  return launch_kernel<rpt::compact_kernel>("compact_kernel", kRecorded, static_cast<unsigned>(n_groups), rpt::kBlockThreads, 0,
+                                            s, bits, seg_counts, n_segs, group_offs, row_sel, out_sel);
 }
 
 int rpt_bf_probe_phase2(const rpt_bf* bf, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
@@ -1857,10 +1640,11 @@ int rpt_bf_probe(const rpt_bf* bf, const rpt_key_column* col, const uint32_t* ro
     hipStream_t s = as_stream(stream);
     RPT_SETTLE(bf, s);
     const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
-    RPT_DISPATCH_KD(launch_probe_small_t, col->key_type, dense_ok(col, row_sel), s, bf, a, n, row_sel, out_sel,
-                    out_count_dev);
-    RPT_LAUNCHED("probe_small_kernel");
-    return RPT_OK;
+    return dispatch_kd(col->key_type, dense_ok(col, row_sel), [&](auto k, auto d) {
+      return launch_kernel<rpt::probe_small_kernel<k(), d()>, k(), d()>(
+          "probe_small_kernel", kRecorded, 1, rpt::kSmallThreads, 0, s, bf->words, (1ULL << bf->log_num_blocks) - 1, a, n,
+          row_sel, out_sel, out_count_dev);
+    });
   }
   bool done = false;
   int st = probe_phase1_impl(bf, col, row_sel, n, workspace, workspace_bytes, stream, out_sel, out_count_dev, &done);
@@ -1896,12 +1680,8 @@ int rpt_bf_probe_chain(const rpt_bf* const* filters, const rpt_key_column* cols,
   }
   if (!out_sel) return fail(RPT_ERR_INVALID_ARGUMENT, "null out_sel");
   for (uint32_t f = 0; f < n_filters; f++) RPT_SETTLE(filters[f], s);
-  ProfScope prof("probe_chain_small_kernel", s);
-  hipLaunchKernelGGL(rpt::probe_chain_small_kernel, dim3(1), dim3(rpt::kSmallThreads), 0, s, c, n, row_sel, out_sel,
-                     out_count_dev);
-  prof.end();
-  RPT_LAUNCHED("probe_chain_small_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::probe_chain_small_kernel>("probe_chain_small_kernel", kRecorded, 1, rpt::kSmallThreads, 0, s, c, n,
+                                                      row_sel, out_sel, out_count_dev);
 }
 
 // ---- the chain for batches of any size ---------------------------------------------------------------------
@@ -1997,25 +1777,19 @@ static int enqueue_chain_later_stages(const rpt_bf* const* filters, const rpt_ke
       const uint64_t n_units = n_segs * (rpt::kWordsPerSeg / 2);
       const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(
           1, std::min<uint64_t>(ceil_div(n_units, rpt::kBlockThreads), static_cast<uint64_t>(num_cus(device)) * rpt::kBlocksPerCU)));
-      ProfScope prof("bits_and_count_kernel", s);
-      hipLaunchKernelGGL(rpt::bits_and_count_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, s, ws.bits, ws.tmp_bits,
-                         n_segs, ws.seg_counts);
-      prof.end();
-      RPT_LAUNCHED("bits_and_count_kernel");
+      RPT_TRY(launch_kernel<rpt::bits_and_count_kernel>("bits_and_count_kernel", kRecorded, grid, rpt::kBlockThreads, 0, s,
+                                                        ws.bits, ws.tmp_bits, n_segs, ws.seg_counts));
       continue;
     }
     const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
-    const bool dense = dense_ok(col, row_sel);
-    if (strategy[f] == RPT_PROBE_GATHER) {
-      const unsigned grid = persistent_grid(device, n_segs);
-      RPT_DISPATCH_KD(launch_probe_bits_masked_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
-      RPT_LAUNCHED("probe_bits_masked_kernel");
-    } else {  // RPT_PROBE_LDS
-      const unsigned grid = lds_probe_grid(device, bf->log_num_blocks, n_segs);
-      RPT_DISPATCH_KD(launch_probe_bits_masked_lds_t, col->key_type, dense, grid, s, bf, a, n, n_segs, ws.bits,
-                      ws.seg_counts);
-      RPT_LAUNCHED("probe_bits_masked_kernel<lds>");
-    }
+    const bool gather = strategy[f] == RPT_PROBE_GATHER;  // else RPT_PROBE_LDS
+    const unsigned grid = gather ? persistent_grid(device, n_segs) : lds_probe_grid(device, bf->log_num_blocks, n_segs);
+    RPT_TRY(dispatch_kd(col->key_type, dense_ok(col, row_sel), [&](auto k, auto d) {
+      if (!gather) return launch_probe_bits_masked_lds_t<k(), d()>(grid, s, bf, a, n, n_segs, ws.bits, ws.seg_counts);
+      return launch_kernel<rpt::probe_bits_masked_kernel<k(), d(), false>, k(), d(), false, rpt::kBlockThreads>(
+          "probe_bits_masked_kernel", kRecorded, grid, rpt::kBlockThreads, 0, s, bf->words, (1ULL << bf->log_num_blocks) - 1,
+          a, n, n_segs, ws.bits, ws.seg_counts);
+    }));
   }
   return RPT_OK;
 }
@@ -2101,12 +1875,8 @@ int rpt_keys_widen(const uint32_t* lo, const uint32_t* chunk_hi, const uint32_t*
   if (n_chunks == 0) return RPT_OK;
   if (!lo || !chunk_hi || !chunk_row0 || !out) return fail(RPT_ERR_INVALID_ARGUMENT, "null argument");
   if (n_chunks > 0x7FFFFFFFu) return fail(RPT_ERR_INVALID_ARGUMENT, "too many chunks");
-  ProfScope prof_w("widen_keys_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::widen_keys_kernel, dim3(static_cast<unsigned>(n_chunks)), dim3(rpt::kWidenThreads), 0,
-                     as_stream(stream), lo, chunk_hi, chunk_row0, out);
-  prof_w.end();
-  RPT_LAUNCHED("widen_keys_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::widen_keys_kernel>("widen_keys_kernel", kRecorded, static_cast<unsigned>(n_chunks),
+                                               rpt::kWidenThreads, 0, as_stream(stream), lo, chunk_hi, chunk_row0, out);
 }
 
 int rpt_words_or_slices(uint64_t* dst, const uint64_t* srcs, uint32_t k, uint64_t n_words, rpt_stream_t stream) {
@@ -2119,12 +1889,8 @@ int rpt_words_or_slices(uint64_t* dst, const uint64_t* srcs, uint32_t k, uint64_
     return fail(RPT_ERR_INVALID_ARGUMENT, "n_words=%llu is odd: with k >= 2 every second slice would not be 16-byte aligned",
                 static_cast<unsigned long long>(n_words));
   const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n_words / 2, rpt::kBlockThreads), 8192)));
-  ProfScope prof12_("or_slices_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::or_slices_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, as_stream(stream), dst, srcs, k,
-                     n_words, n_words, 0);
-  prof12_.end();
-  RPT_LAUNCHED("or_slices_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::or_slices_kernel>("or_slices_kernel", kRecorded, grid, rpt::kBlockThreads, 0, as_stream(stream),
+                                              dst, srcs, k, n_words, n_words, 0);
 }
 
 int rpt_words_or(uint64_t* dst, const uint64_t* src, uint64_t n_words, rpt_stream_t stream) {
@@ -2132,12 +1898,8 @@ int rpt_words_or(uint64_t* dst, const uint64_t* src, uint64_t n_words, rpt_strea
   if (n_words == 0) return RPT_OK;
   if (misaligned16(dst) || misaligned16(src)) return fail(RPT_ERR_INVALID_ARGUMENT, "dst and src must be 16-byte aligned");
   const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n_words / 2, rpt::kBlockThreads), 8192)));
-  ProfScope prof13_("or_slices_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::or_slices_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, as_stream(stream), dst, src, 1u,
-                     n_words, n_words, 1);
-  prof13_.end();
-  RPT_LAUNCHED("or_slices_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::or_slices_kernel>("or_slices_kernel", kRecorded, grid, rpt::kBlockThreads, 0, as_stream(stream),
+                                              dst, src, 1u, n_words, n_words, 1);
 }
 
 int rpt_bf_merge_or(rpt_bf* dst, const rpt_bf* src, rpt_stream_t stream) {
@@ -2153,12 +1915,9 @@ int rpt_bf_merge_or(rpt_bf* dst, const rpt_bf* src, rpt_stream_t stream) {
   const hipError_t ez = zero_pending_locked(dst, as_stream(stream));
   if (ez != hipSuccess) return fail(RPT_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez));
   int st = rpt_words_or(dst->words, src->words, 1ULL << dst->log_num_blocks, stream);
-  if (st == RPT_OK) {
-    // inside the write order: a later clear's stats reset must not be overtaken by this merge
-    hipLaunchKernelGGL(stats_merge_kernel, dim3(1), dim3(1), 0, as_stream(stream), dst->stats, src->stats);
-    const hipError_t el = hipGetLastError();
-    if (el != hipSuccess) st = fail(RPT_ERR_HIP, "launch of stats_merge_kernel failed: %s", hipGetErrorString(el));
-  }
+  if (st == RPT_OK)  // inside the write order: a later clear's stats reset must not be overtaken by this merge
+    st = launch_kernel<stats_merge_kernel>("stats_merge_kernel", kUnrecorded, 1, 1, 0, as_stream(stream), dst->stats,
+                                           src->stats);
   order.done(false);
   if (st != RPT_OK) return st;
   if (src->has_data.load()) dst->has_data.store(1);
@@ -2508,11 +2267,9 @@ int rpt_bf_allreduce_or_ws(rpt_bf* bf, void* nccl_comm, void* workspace, size_t 
           RPT_HIP(hipStreamWaitEvent(h->s, h->rx[b], 0));
           helper_pending = true;
           const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(cnt / 2 + 1, rpt::kBlockThreads), 2048)));
-          ProfScope prof_or("or_slices_kernel(allreduce)", h->s);
-          hipLaunchKernelGGL(rpt::or_slices_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, h->s,
-                             bf->words + g.lo(me) + r * R, buf, static_cast<uint32_t>(world - 1), cnt, stride, 1);
-          prof_or.end();
-          RPT_LAUNCHED("or_slices_kernel");
+          RPT_TRY(launch_kernel<rpt::or_slices_kernel>("or_slices_kernel(allreduce)", kRecorded, grid, rpt::kBlockThreads, 0,
+                                                       h->s, bf->words + g.lo(me) + r * R, buf,
+                                                       static_cast<uint32_t>(world - 1), cnt, stride, 1));
           RPT_HIP(hipEventRecord(h->ored[b], h->s));
           ored[b] = true;
         }
@@ -2527,12 +2284,11 @@ int rpt_bf_allreduce_or_ws(rpt_bf* bf, void* nccl_comm, void* workspace, size_t 
       }
       RPT_NCCL_MERGE(api.group_end());
     }
-    hipLaunchKernelGGL(minmax_pack_kernel, dim3(1), dim3(1), 0, s, bf->stats, bf->has_data.load(), v);
-    RPT_LAUNCHED("minmax_pack_kernel");
+    RPT_TRY(launch_kernel<minmax_pack_kernel>("minmax_pack_kernel", kUnrecorded, 1, 1, 0, s, bf->stats, bf->has_data.load(), v));
     posted = true;
     RPT_NCCL_MERGE(api.all_reduce(v, v, 3, kNcclInt64, kNcclMin, nccl_comm, s));
-    hipLaunchKernelGGL(minmax_unpack_kernel, dim3(1), dim3(1), 0, s, v, bf->stats, reinterpret_cast<int*>(v + 3));
-    RPT_LAUNCHED("minmax_unpack_kernel");
+    RPT_TRY(launch_kernel<minmax_unpack_kernel>("minmax_unpack_kernel", kUnrecorded, 1, 1, 0, s, v, bf->stats,
+                                                reinterpret_cast<int*>(v + 3)));
     // bounded wait for everything enqueued above (never a blind hipStreamSynchronize: see poll_streams)
     std::string why;
     const int ws = poll_streams(&api, nccl_comm, {s}, deadline, &why);
@@ -2737,13 +2493,14 @@ int rpt_bf_count_bits(const rpt_bf* bf, uint64_t* out) {
   hipError_t e = hipMemset(d, 0, sizeof(unsigned long long));
   const uint64_t nw = 1ULL << bf->log_num_blocks;
   const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(nw, rpt::kBlockThreads), 4096)));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(rpt::popcount_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, nullptr, bf->words, nw, d);
-    e = hipGetLastError();
-  }
+  int st = RPT_OK;
+  if (e == hipSuccess)
+    st = launch_kernel<rpt::popcount_kernel>("popcount_kernel", kUnrecorded, grid, rpt::kBlockThreads, 0, nullptr, bf->words,
+                                             nw, d);
   unsigned long long h = 0;
-  if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && st == RPT_OK) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
   (void)hipFree(d);
+  if (st != RPT_OK) return st;
   if (e != hipSuccess) return fail(RPT_ERR_HIP, "count_bits: %s", hipGetErrorString(e));
   *out = h;
   return RPT_OK;
@@ -2769,13 +2526,14 @@ int rpt_bf_is_same_as(const rpt_bf* a, const rpt_bf* b, int* out_same, uint64_t*
   const unsigned grid =
       static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(nw / 2, rpt::kBlockThreads),
                                                                       static_cast<uint64_t>(num_cus(a->device)) * rpt::kBlocksPerCU)));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(rpt::diff_count_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, nullptr, a->words, b->words, nw, d);
-    e = hipGetLastError();
-  }
+  int st = RPT_OK;
+  if (e == hipSuccess)
+    st = launch_kernel<rpt::diff_count_kernel>("diff_count_kernel", kUnrecorded, grid, rpt::kBlockThreads, 0, nullptr,
+                                               a->words, b->words, nw, d);
   unsigned long long h = 0;
-  if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && st == RPT_OK) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
   (void)hipFree(d);
+  if (st != RPT_OK) return st;
   if (e != hipSuccess) return fail(RPT_ERR_HIP, "is_same_as: %s", hipGetErrorString(e));
   *out_same = h == 0;
   if (out_diff_words) *out_diff_words = h;
@@ -2806,11 +2564,9 @@ int rpt_bf_fold(rpt_bf* bf, int* out_new_log_num_blocks) {
     const uint64_t slice = nb >> folds;
     // target slice 0 accumulates slices 1 .. 2^folds-1 (they never overlap the target)
     const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(slice / 2, rpt::kBlockThreads), 8192)));
-    ProfScope prof14_("or_slices_kernel(fold)", nullptr);
-    hipLaunchKernelGGL(rpt::or_slices_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, nullptr, bf->words,
-                       bf->words + slice, static_cast<uint32_t>((1u << folds) - 1), slice, slice, 1);
-    prof14_.end();
-    RPT_LAUNCHED("or_slices_kernel(fold)");
+    RPT_TRY(launch_kernel<rpt::or_slices_kernel>("or_slices_kernel(fold)", kRecorded, grid, rpt::kBlockThreads, 0, nullptr,
+                                                 bf->words, bf->words + slice, static_cast<uint32_t>((1u << folds) - 1), slice,
+                                                 slice, 1));
     RPT_HIP(hipDeviceSynchronize());
     bf->log_num_blocks -= folds;
   }
@@ -2931,11 +2687,8 @@ int rpt_synth_build_keys(int64_t* out, uint64_t start, uint64_t n, rpt_stream_t 
   if (!out) return fail(RPT_ERR_INVALID_ARGUMENT, "null out");
   if (n == 0) return RPT_OK;
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(ceil_div(n, rpt::kBlockThreads), 8192));
-  ProfScope prof15_("synth_build_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::synth_build_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, as_stream(stream), out, start, n);
-  prof15_.end();
-  RPT_LAUNCHED("synth_build_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::synth_build_kernel>("synth_build_kernel", kRecorded, grid, rpt::kBlockThreads, 0, as_stream(stream),
+                                                out, start, n);
 }
 
 int rpt_synth_probe_keys(int64_t* out, uint64_t n_build, uint32_t p_permille, uint64_t start, uint64_t n,
@@ -2944,12 +2697,8 @@ int rpt_synth_probe_keys(int64_t* out, uint64_t n_build, uint32_t p_permille, ui
   if (p_permille > 1000) return fail(RPT_ERR_INVALID_ARGUMENT, "p_permille %u > 1000", p_permille);
   if (n == 0) return RPT_OK;
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(ceil_div(n, rpt::kBlockThreads), 8192));
-  ProfScope prof16_("synth_probe_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::synth_probe_kernel, dim3(grid), dim3(rpt::kBlockThreads), 0, as_stream(stream), out, n_build,
-                     p_permille, start, n);
-  prof16_.end();
-  RPT_LAUNCHED("synth_probe_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::synth_probe_kernel>("synth_probe_kernel", kRecorded, grid, rpt::kBlockThreads, 0, as_stream(stream),
+                                                out, n_build, p_permille, start, n);
 }
 
 uint64_t rpt_stream_sink_words(int device) { return static_cast<uint64_t>(num_cus(device)) * rpt::kStreamBlocksPerCU; }
@@ -2968,12 +2717,9 @@ int rpt_stream_read(const void* src, uint64_t bytes, uint64_t* sink, rpt_stream_
   if (st != RPT_OK) return st;
   if (!sink) return fail(RPT_ERR_INVALID_ARGUMENT, "null sink");
   if (bytes == 0) return RPT_OK;
-  ProfScope prof_("stream_read_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::stream_read_kernel, dim3(static_cast<unsigned>(rpt_stream_sink_words(dev))),
-                     dim3(rpt::kBlockThreads), 0, as_stream(stream), static_cast<const rpt::u64x2*>(src), bytes / 16, sink);
-  prof_.end();
-  RPT_LAUNCHED("stream_read_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::stream_read_kernel>("stream_read_kernel", kRecorded, static_cast<unsigned>(rpt_stream_sink_words(dev)),
+                                                rpt::kBlockThreads, 0, as_stream(stream), static_cast<const rpt::u64x2*>(src),
+                                                bytes / 16, sink);
 }
 
 int rpt_stream_copy(void* dst, const void* src, uint64_t bytes, rpt_stream_t stream) {
@@ -2983,13 +2729,9 @@ int rpt_stream_copy(void* dst, const void* src, uint64_t bytes, rpt_stream_t str
   if (st != RPT_OK) return st;
   if (bytes == 0) return RPT_OK;
   if (ceil_div(bytes / 16, rpt::kBlockThreads) > 0x7fffffffULL) return fail(RPT_ERR_INVALID_ARGUMENT, "copy too large");
-  ProfScope prof_("stream_copy_kernel", as_stream(stream));
-  hipLaunchKernelGGL(rpt::stream_copy_kernel, dim3(static_cast<unsigned>(ceil_div(bytes / 16, rpt::kBlockThreads))),
-                     dim3(rpt::kBlockThreads), 0, as_stream(stream), static_cast<const rpt::u64x2*>(src), bytes / 16,
-                     static_cast<rpt::u64x2*>(dst));
-  prof_.end();
-  RPT_LAUNCHED("stream_copy_kernel");
-  return RPT_OK;
+  return launch_kernel<rpt::stream_copy_kernel>(
+      "stream_copy_kernel", kRecorded, static_cast<unsigned>(ceil_div(bytes / 16, rpt::kBlockThreads)), rpt::kBlockThreads, 0,
+      as_stream(stream), static_cast<const rpt::u64x2*>(src), bytes / 16, static_cast<rpt::u64x2*>(dst));
 }
 
 }  // extern "C"

@@ -5,47 +5,25 @@
 // tests/kernel_ledger_range.py (tests/test_kernel_ledger_range_names.py scans this file).
 #pragma once
 
-extern "C++" {
 namespace {
-
-template <int K, bool D, bool M>
-void launch_range_bits_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a, uint64_t n,
-                         uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
-  ProfScope prof(inst_name<K, D, M>("range_bits_kernel"), s);
-  hipLaunchKernelGGL((rpt::range_bits_kernel<K, D, M>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->stats, a, n,
-                     n_segs, bits, counts);
-  prof.end();
-}
 
 // The range test of one column (I64 or I32: the caller has refused HASH) over n rows. masked: AND into the accumulated
 // bits / counts in place; else write every segment's words (and its count where counts != nullptr).
-template <bool M>
-void launch_range_bits_m(int key_type, bool dense, unsigned grid, hipStream_t s, const rpt_bf* bf,
-                         const rpt::KeyArgs& a, uint64_t n, uint64_t n_segs, uint64_t* bits, uint32_t* counts) {
-  if (key_type == RPT_KEY_I64) {
-    if (dense) launch_range_bits_t<rpt::kKeyI64, true, M>(grid, s, bf, a, n, n_segs, bits, counts);
-    else launch_range_bits_t<rpt::kKeyI64, false, M>(grid, s, bf, a, n, n_segs, bits, counts);
-  } else {
-    if (dense) launch_range_bits_t<rpt::kKeyI32, true, M>(grid, s, bf, a, n, n_segs, bits, counts);
-    else launch_range_bits_t<rpt::kKeyI32, false, M>(grid, s, bf, a, n, n_segs, bits, counts);
-  }
-}
-
-}  // namespace
-}  // extern "C++"
-
-namespace {
-
 int enqueue_range_stage(const rpt_bf* bf, const rpt_key_column* col, const uint32_t* row_sel, uint64_t n, bool masked,
                         uint64_t* bits, uint32_t* counts, hipStream_t s) {
   const uint64_t n_segs = ceil_div(n, rpt::kSegRows);
   const unsigned grid = persistent_grid(bf->device, n_segs);
   const rpt::KeyArgs a{col->keys, col->key_sel, col->validity, row_sel};
-  const bool dense = dense_ok(col, row_sel);
-  if (masked) launch_range_bits_m<true>(col->key_type, dense, grid, s, bf, a, n, n_segs, bits, counts);
-  else launch_range_bits_m<false>(col->key_type, dense, grid, s, bf, a, n, n_segs, bits, counts);
-  RPT_LAUNCHED("range_bits_kernel");
-  return RPT_OK;
+  return dispatch_kd(col->key_type, dense_ok(col, row_sel), [&](auto k, auto d) {
+    if constexpr (!rpt::KeyTraits<k()>::kValues) {
+      return fail(RPT_ERR_INVALID_ARGUMENT, "range test of a column that holds hashes (no key values)");  // callers refuse it
+    } else {
+      return dispatch_bool(masked, [&](auto m) {
+        return launch_kernel<rpt::range_bits_kernel<k(), d(), m()>, k(), d(), m()>(
+            "range_bits_kernel", kRecorded, grid, rpt::kBlockThreads, 0, s, bf->stats, a, n, n_segs, bits, counts);
+      });
+    }
+  });
 }
 
 // What a range call (range_mask != 0) checks after its lists and before any handle is looked into: the mask, every

@@ -1,39 +1,36 @@
 // rpt_probe_sel.hpp — the device-counted probes: rpt_bf_probe_chain_sel_ws, rpt_bf_transfer_sel_ws,
 // rpt_bf_transfer_insert_sel_ws, their sizing and strategy functions, and the launcher of their first stage
 // (kernels/probe_sel.hpp). Host code of librpt_gpu.so, included by rpt_gpu.hip inside its extern "C" block, after
-// rpt_chain_call.hpp, whose run_chain_call is the body of the entry points. Every kernel recorded here has a row in
-// tests/kernel_ledger_sel.py (tests/test_kernel_ledger_sel_names.py scans this file).
+// rpt_chain_call.hpp, whose run_chain_call is the body of the entry points; the launches go through launch_kernel
+// (rpt_launch.hpp). Every kernel recorded here has a row in tests/kernel_ledger_sel.py
+// (tests/test_kernel_ledger_sel_names.py scans this file).
 #pragma once
 
 extern "C++" {
 namespace {
 
+// The first stage of a device-counted chain over a column of key type K: the gather, or the filter (LDS) or its first
+// 128 KiB (hybrid) staged in LDS.
 template <int K, int MODE>
-void launch_probe_bits_sel_m(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a,
-                             const uint64_t* count_dev, uint64_t max_rows, uint64_t n_segs, uint64_t* bits,
-                             uint32_t* counts) {
-  size_t lds = 0;
-  if constexpr (MODE != rpt::kSelGather) {
-    lds = 8ULL << std::min(bf->log_num_blocks, rpt::kLdsDirectMaxLog);
-    static std::once_flag once;  // per instantiation; > 64 KiB of dynamic LDS must be opted into
-    std::call_once(once, [] { allow_dynamic_lds(reinterpret_cast<const void*>(&rpt::probe_bits_sel_kernel<K, MODE>)); });
-  }
-  ProfScope prof(inst_name<K, MODE>("probe_bits_sel_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_bits_sel_kernel<K, MODE>), dim3(grid), dim3(rpt::sel_probe_threads<MODE>()), lds, s,
-                     bf->words, (1ULL << bf->log_num_blocks) - 1, a, count_dev, max_rows, n_segs, bits, counts);
-  prof.end();
+int launch_probe_bits_sel_m(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a,
+                            const uint64_t* count_dev, uint64_t max_rows, uint64_t n_segs, uint64_t* bits,
+                            uint32_t* counts) {
+  constexpr bool kInLds = MODE != rpt::kSelGather;
+  return launch_kernel<rpt::probe_bits_sel_kernel<K, MODE>, K, MODE>(
+      "probe_bits_sel_kernel", kRecorded | (kInLds ? kDynamicLds : 0), grid, rpt::sel_probe_threads<MODE>(),
+      kInLds ? 8ULL << std::min(bf->log_num_blocks, rpt::kLdsDirectMaxLog) : 0, s, bf->words,
+      (1ULL << bf->log_num_blocks) - 1, a, count_dev, max_rows, n_segs, bits, counts);
 }
 
 template <int K>
-void launch_probe_bits_sel_k(int strategy, unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a,
-                             const uint64_t* count_dev, uint64_t max_rows, uint64_t n_segs, uint64_t* bits,
-                             uint32_t* counts) {
+int launch_probe_bits_sel_k(int strategy, unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a,
+                            const uint64_t* count_dev, uint64_t max_rows, uint64_t n_segs, uint64_t* bits,
+                            uint32_t* counts) {
   if (strategy == RPT_PROBE_GATHER)
-    launch_probe_bits_sel_m<K, rpt::kSelGather>(grid, s, bf, a, count_dev, max_rows, n_segs, bits, counts);
-  else if (bf->log_num_blocks <= rpt::kLdsDirectMaxLog)
-    launch_probe_bits_sel_m<K, rpt::kSelLds>(grid, s, bf, a, count_dev, max_rows, n_segs, bits, counts);
-  else
-    launch_probe_bits_sel_m<K, rpt::kSelHybrid>(grid, s, bf, a, count_dev, max_rows, n_segs, bits, counts);
+    return launch_probe_bits_sel_m<K, rpt::kSelGather>(grid, s, bf, a, count_dev, max_rows, n_segs, bits, counts);
+  if (bf->log_num_blocks <= rpt::kLdsDirectMaxLog)
+    return launch_probe_bits_sel_m<K, rpt::kSelLds>(grid, s, bf, a, count_dev, max_rows, n_segs, bits, counts);
+  return launch_probe_bits_sel_m<K, rpt::kSelHybrid>(grid, s, bf, a, count_dev, max_rows, n_segs, bits, counts);
 }
 
 }  // namespace
@@ -55,19 +52,9 @@ int enqueue_sel_stage0(const ChainCall& c, int strategy, int device, const Chain
   const rpt::KeyArgs a{col.keys, col.key_sel, col.validity, c.sel};
   const unsigned grid = strategy == RPT_PROBE_GATHER ? persistent_grid(device, n_segs)
                                                      : lds_probe_grid(device, bf->log_num_blocks, n_segs);
-  switch (col.key_type) {
-    case RPT_KEY_I64:
-      launch_probe_bits_sel_k<rpt::kKeyI64>(strategy, grid, s, bf, a, c.count_dev, c.n, n_segs, ws.bits, ws.seg_counts);
-      break;
-    case RPT_KEY_I32:
-      launch_probe_bits_sel_k<rpt::kKeyI32>(strategy, grid, s, bf, a, c.count_dev, c.n, n_segs, ws.bits, ws.seg_counts);
-      break;
-    default:
-      launch_probe_bits_sel_k<rpt::kKeyHash>(strategy, grid, s, bf, a, c.count_dev, c.n, n_segs, ws.bits, ws.seg_counts);
-      break;
-  }
-  RPT_LAUNCHED("probe_bits_sel_kernel");
-  return RPT_OK;
+  return dispatch_k(col.key_type, [&](auto k) {
+    return launch_probe_bits_sel_k<k()>(strategy, grid, s, bf, a, c.count_dev, c.n, n_segs, ws.bits, ws.seg_counts);
+  });
 }
 }  // namespace
 

@@ -7,31 +7,6 @@
 // this file).
 #pragma once
 
-extern "C++" {
-namespace {
-
-template <int K>
-void launch_range_bits_sel_t(unsigned grid, hipStream_t s, const rpt_bf* bf, const rpt::KeyArgs& a,
-                             const uint64_t* count_dev, uint64_t max_rows, uint64_t n_segs, uint64_t* bits,
-                             uint32_t* counts) {
-  ProfScope prof(inst_name<K>("range_bits_sel_kernel"), s);
-  hipLaunchKernelGGL((rpt::range_bits_sel_kernel<K>), dim3(grid), dim3(rpt::kBlockThreads), 0, s, bf->stats, a,
-                     count_dev, max_rows, n_segs, bits, counts);
-  prof.end();
-}
-
-template <bool COUNTED, bool TRANSFER>
-void launch_probe_chain_range_small_t(hipStream_t s, const rpt::RangeChainArgs& r, const rpt::DstArgs& d,
-                                      const ChainCall& c) {
-  ProfScope prof(inst_name<COUNTED, TRANSFER>("probe_chain_range_small_kernel"), s);
-  hipLaunchKernelGGL((rpt::probe_chain_range_small_kernel<COUNTED, TRANSFER>), dim3(1), dim3(rpt::kSmallThreads), 0, s, r,
-                     d, c.sel, c.count_dev, c.n, c.out_sel, c.out_count_dev);
-  prof.end();
-}
-
-}  // namespace
-}  // extern "C++"
-
 namespace {
 
 // Stage 0 of a ranged device-counted call: the first flagged column's range stage over sel[0 .. min(*count_dev,
@@ -53,11 +28,13 @@ int enqueue_sel_range_stages(const ChainCall& c, const ChainWorkspace& ws, hipSt
     const uint64_t n_segs = ceil_div(c.n, rpt::kSegRows);
     const unsigned grid = persistent_grid(bf->device, n_segs);
     const rpt::KeyArgs a{col.keys, col.key_sel, col.validity, c.sel};
-    if (col.key_type == RPT_KEY_I64)  // I64 or I32: check_range_mask has refused a flagged HASH column
-      launch_range_bits_sel_t<rpt::kKeyI64>(grid, s, bf, a, c.count_dev, c.n, n_segs, ws.bits, ws.seg_counts);
-    else
-      launch_range_bits_sel_t<rpt::kKeyI32>(grid, s, bf, a, c.count_dev, c.n, n_segs, ws.bits, ws.seg_counts);
-    RPT_LAUNCHED("range_bits_sel_kernel");
+    auto launch = [&](auto k) {
+      return launch_kernel<rpt::range_bits_sel_kernel<k()>, k()>("range_bits_sel_kernel", kRecorded, grid, rpt::kBlockThreads, 0,
+                                                                 s, bf->stats, a, c.count_dev, c.n, n_segs, ws.bits,
+                                                                 ws.seg_counts);
+    };
+    // I64 or I32: check_range_mask has refused a flagged HASH column
+    RPT_TRY(col.key_type == RPT_KEY_I64 ? launch(int_c<rpt::kKeyI64>{}) : launch(int_c<rpt::kKeyI32>{}));
   }
   return RPT_OK;
 }
@@ -120,12 +97,16 @@ int probe_chain_range_small_impl(const ChainCall& c) {
   WriteOrders orders;
   st = take_write_orders(c, s, orders);
   if (st != RPT_OK) return st;
-  if (c.transfer) launch_probe_chain_range_small_t<true, true>(s, r, d, c);
-  else if (c.counted) launch_probe_chain_range_small_t<true, false>(s, r, d, c);
-  else launch_probe_chain_range_small_t<false, false>(s, r, d, c);
+  auto launch = [&](auto counted, auto transfer) {
+    return launch_kernel<rpt::probe_chain_range_small_kernel<counted(), transfer()>, counted(), transfer()>(
+        "probe_chain_range_small_kernel", kRecorded, 1, rpt::kSmallThreads, 0, s, r, d, c.sel, c.count_dev, c.n, c.out_sel,
+        c.out_count_dev);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  st = c.transfer ? launch(yes, yes) : c.counted ? launch(yes, no) : launch(no, no);
   for (uint32_t i = 0; i < orders.n; i++) orders[i].done(false);
-  RPT_LAUNCHED("probe_chain_range_small_kernel");
-  return RPT_OK;
+  return st;
 }
 }  // namespace
 

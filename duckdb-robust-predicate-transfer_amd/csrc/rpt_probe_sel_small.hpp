@@ -90,20 +90,13 @@ int probe_chain_sel_small_impl(const ChainCall& c) {
   WriteOrders orders;
   st = take_write_orders(c, s, orders);
   if (st != RPT_OK) return st;
-  if (c.transfer) {
-    ProfScope prof(inst_name<true>("probe_chain_sel_small_kernel"), s);
-    hipLaunchKernelGGL(rpt::probe_chain_sel_small_kernel<true>, dim3(1), dim3(rpt::kSmallThreads), 0, s, a, d, c.sel,
-                       c.count_dev, c.n, c.out_sel, c.out_count_dev);
-    prof.end();
-  } else {
-    ProfScope prof(inst_name<false>("probe_chain_sel_small_kernel"), s);
-    hipLaunchKernelGGL(rpt::probe_chain_sel_small_kernel<false>, dim3(1), dim3(rpt::kSmallThreads), 0, s, a, d, c.sel,
-                       c.count_dev, c.n, c.out_sel, c.out_count_dev);
-    prof.end();
-  }
+  st = dispatch_bool(c.transfer, [&](auto transfer) {
+    return launch_kernel<rpt::probe_chain_sel_small_kernel<transfer()>, transfer()>(
+        "probe_chain_sel_small_kernel", kRecorded, 1, rpt::kSmallThreads, 0, s, a, d, c.sel, c.count_dev, c.n, c.out_sel,
+        c.out_count_dev);
+  });
   for (uint32_t i = 0; i < orders.n; i++) orders[i].done(false);
-  RPT_LAUNCHED("probe_chain_sel_small_kernel");
-  return RPT_OK;
+  return st;
 }
 }  // namespace
 

@@ -1,7 +1,7 @@
 """The kernel ledger: which kernel instantiation each small call through the C-ABI must launch (imported as a plain
 module, like buf_util; not a conftest, and it needs neither torch nor a GPU).
 
-librpt_gpu.so picks one of about 110 kernel instantiations at run time (RPT_DISPATCH_KD, launch_partition_tm,
+librpt_gpu.so picks one of about 110 kernel instantiations at run time (dispatch_kd, launch_partition_tm,
 launch_probe_bits_lds_t, launch_bucket_scatter_t and the strategy resolvers in csrc/rpt_gpu.hip) and records every
 launch under its instantiation name (rpt_profiling_*: "partition_kernel<0,true,false,1,0>"). ROWS lists one small
 call per instantiation the product build can reach, with the exact set of names, and launches of each, the call must
@@ -59,7 +59,7 @@ INS_ATOMIC, INS_PARTITIONED, INS_BUCKETED = 1, 2, 3  # rpt_insert_strategy
 
 
 def targ(v) -> str:
-    """A template argument as inst_name<> spells it."""
+    """A template argument as recorded_name<> (csrc/rpt_launch.hpp) spells it."""
     return ("true" if v else "false") if isinstance(v, bool) else str(int(v))
 
 
@@ -68,7 +68,7 @@ def inst(base: str, *args) -> str:
 
 
 def kd_product(base: str, *extra):
-    """Every name of a K x D dispatch (RPT_DISPATCH_KD): base<K,D,extra...>."""
+    """Every name of a K x D dispatch (dispatch_kd): base<K,D,extra...>."""
     return [inst(base, k, d, *extra) for k in KEYS.values() for d in (True, False)]
 
 
@@ -232,23 +232,15 @@ def expected_names(rows=None) -> set:
 
 
 def source_base_names(path: str = HOST_SOURCE) -> set:
-    """The base name of every kernel the host runtime can record: the string literals given to ProfScope and
-    inst_name in csrc/rpt_gpu.hip (a ProfScope may choose between literals: every one in its argument counts)."""
+    """The base name of every kernel the host runtime can record: the name literal of every launch_kernel<...>() call
+    in csrc/rpt_gpu.hip (csrc/rpt_launch.hpp) that is kRecorded; a kUnrecorded call contributes no name."""
     with open(path) as f:
         src = f.read()
-    names = set()
-    scopes = list(re.finditer(r"\bProfScope\s+\w+\s*\(([^;]*?),\s*[\w>()-]+\s*\)\s*;", src, re.S))
-    # every ProfScope variable of the source was understood (a new spelling must not slip through unseen)
-    if len(scopes) != len(re.findall(r"\bProfScope\s+\w+\s*\(", src)):
-        raise AssertionError("a ProfScope in %s is spelled in a way source_base_names() does not parse" % path)
-    for m in scopes:
-        literals = re.findall(r'"([^"]+)"', m.group(1))
-        if not literals:
-            raise AssertionError("ProfScope without a name literal: %s" % m.group(0))
-        names.update(base_name(s) for s in literals)
-    for m in re.finditer(r"\binst_name\s*<[^;]*?>\s*\(\s*\"([^\"]+)\"\s*\)", src, re.S):
-        names.add(base_name(m.group(1)))
-    return names
+    calls = re.findall(r"\blaunch_kernel\s*<[^;\"]*?>\s*\(\s*\"([^\"]+)\"\s*,\s*(kRecorded|kUnrecorded)\b", src, re.S)
+    # every launch_kernel call of the source was understood (a new spelling must not slip through unseen)
+    if len(calls) != len(re.findall(r"\blaunch_kernel\s*<", src)):
+        raise AssertionError("a launch_kernel call in %s is spelled in a way source_base_names() does not parse" % path)
+    return {base_name(name) for name, flag in calls if flag == "kRecorded"}
 
 
 def kernel_set_problems(expected: dict, observed: dict) -> list:

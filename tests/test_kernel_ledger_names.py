@@ -2,13 +2,16 @@
 has a row or a written exemption, every K x D dispatch is covered as the full product, no expected name is cut or
 collides in rpt_kernel_stat::name, and the comparison the GPU test relies on rejects what it should."""
 import collections
+import glob
+import os
+import re
 
 import kernel_ledger as kl
 
 
 def test_every_kernel_of_the_host_runtime_has_a_row_or_an_exemption():
     source = kl.source_base_names()
-    # the scan itself works: a few names of each spelling (plain literal, inst_name<>, a choice between literals)
+    # the scan itself works: a few names of each spelling (plain literal, with name arguments, behind dispatch_tm)
     for name in ("slice_probe_kernel", "partition_kernel", "unpermute_sel_kernel", "hash_kernel", "or_slices_kernel(fold)",
                  "probe_bits_masked_hybrid_kernel", "stream_copy_kernel"):
         assert name in source, name
@@ -30,7 +33,7 @@ def test_exemptions_are_the_agreed_ones_each_with_a_reason():
 
 
 def test_dispatch_products_are_complete():
-    """Every name RPT_DISPATCH_KD and the launchers behind it can produce in the product build."""
+    """Every name dispatch_kd and the launchers behind it can produce in the product build."""
     want = []
     want += kl.kd_product("probe_bits_kernel", False, kl.BLOCK_THREADS)  # GATHER; rpt_bf_find_bits
     want += kl.kd_product("probe_bits_kernel", True, kl.LDS_THREADS)  # LDS, whole filter
@@ -110,3 +113,16 @@ def test_set_comparison_rejects_missing_extra_and_wrong_count():
     # a wrong template argument is both a missing and an extra name
     swapped = {"a_kernel<0,false>": (1, 0.01), "b_kernel": (2, 0.5), "c_kernel(fold)": (1, 0.1)}
     assert [p.split(":")[0] for p in kl.kernel_set_problems(expected, swapped)] == ["missing", "extra"]
+
+
+def test_every_launch_goes_through_the_helper():
+    """csrc/rpt_launch.hpp holds the one hipLaunchKernelGGL of the host runtime; rpt_gpu.hip and the other host headers
+    launch through it and keep no once-flag of their own around the dynamic-LDS opt-in."""
+    helper = os.path.join(kl.CSRC, "rpt_launch.hpp")
+    others = [kl.HOST_SOURCE] + sorted(p for p in glob.glob(os.path.join(kl.CSRC, "rpt_*.hpp")) if p != helper)
+    assert len(others) >= 8 and os.path.isfile(helper), others
+    for path in others:
+        text = open(path).read()
+        assert "hipLaunchKernelGGL" not in text, path
+        assert not re.search(r"std::once_flag.{0,400}?allow_dynamic_lds", text, re.S), path
+    assert open(helper).read().count("hipLaunchKernelGGL") == 1

@@ -9,7 +9,8 @@ Prints one line per kernel: identical / different / only-in-A / only-in-B, with 
 private-segment bytes of its .amdhsa_ block on each side. Kernels are matched by demangled name without the
 parameter list (a kernel that gains or loses an argument is still the same kernel); without a demangler on
 PATH, by symbol. Local labels and the comments that cite them lose their function ordinal first (.LBB<n>_,
-.Lfunc_end<n>): it shifts when a kernel before them is added or removed. The text is compared as text: nothing
+.Lfunc_end<n>): it shifts when a kernel before them is added or removed, and with it the padding before a label's
+comment, which is collapsed to one space. The text is compared as text: nothing
 here reads instructions. Exit status 0; the verdict is the reader's.
 """
 import re
@@ -56,6 +57,7 @@ def kernels(path):
         end = next(i for i in range(start, len(lines)) if re.match(r"\.Lfunc_end\d+:", lines[i]))
         body = "\n".join(lines[start + 1:end])
         body = re.sub(r"BB\d+_", "BB_", body).replace(sym, "<kernel>")
+        body = re.sub(r"[ \t]+;", " ;", body)  # a label's comment is padded to a column: one space less per ordinal digit
         found[names[sym]] = (body, res[sym])
     return found
 
