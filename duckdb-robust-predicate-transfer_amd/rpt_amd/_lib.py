@@ -207,6 +207,17 @@ SIGNATURES = {
         c_int,
         [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p],
     ),
+    "rpt_bf_transfer": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    "rpt_bf_transfer_range": (
+        c_int,
+        [c_void_p, POINTER(KeyColumn), c_uint32, c_uint32, c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "rpt_bf_insert_multi": (c_int, [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p]),
     "rpt_bf_probe_phase1": (
         c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_size_t, c_void_p]
     ),

@@ -66,18 +66,25 @@ def _list_args(filters, columns):
     return (ctypes.c_void_p * len(filters))(*[f._h for f in filters]), (KeyColumn * len(cols))(*cols)
 
 
-def _probed_call_args(filters, columns, row_sel, n, out_sel, out_count):
-    """The probed side of every chain and transfer call: the checked lists as arrays, n (None: the length of row_sel,
-    else of the first column's key_sel, else of its keys), the row_sel check, and out_sel / out_count (allocated here
-    when None)."""
-    _check_lists(filters, columns, "one key column per filter, at least one filter")
-    handles, arr = _list_args(filters, columns)
+def _row_list_rows(columns, row_sel, n) -> int:
+    """n of a row-list call (None: the length of row_sel, else of the first column's key_sel, else of its keys), with
+    the row_sel check."""
     if n is None:
         c0 = columns[0] if isinstance(columns[0], dict) else {"keys": columns[0]}
         n = (row_sel.numel() if row_sel is not None else
              (c0["key_sel"].numel() if c0.get("key_sel") is not None else c0["keys"].numel()))
     if row_sel is not None and (row_sel.element_size() != 4 or not row_sel.is_cuda):
         raise RptError(1, "row_sel must be a 32-bit device tensor")
+    return int(n)
+
+
+def _probed_call_args(filters, columns, row_sel, n, out_sel, out_count):
+    """The probed side of every chain and transfer call: the checked lists as arrays, n (None: the length of row_sel,
+    else of the first column's key_sel, else of its keys), the row_sel check, and out_sel / out_count (allocated here
+    when None)."""
+    _check_lists(filters, columns, "one key column per filter, at least one filter")
+    handles, arr = _list_args(filters, columns)
+    n = _row_list_rows(columns, row_sel, n)
     device = filters[0].device
     if out_sel is None:
         out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
@@ -466,6 +473,47 @@ def probe_chain_range(filters, columns, *, range_mask, row_sel: Optional[torch.T
     check(lib.rpt_bf_probe_chain_range(handles, arr, len(filters), mask, _ptr(row_sel), n, out_sel.data_ptr(),
                                        out_count.data_ptr(), _stream(device, stream)), lib)
     return out_sel[: int(out_count.item())]
+
+
+def transfer(filters, columns, dst_filters, dst_columns, *, row_sel: Optional[torch.Tensor] = None,
+             n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+             out_count: Optional[torch.Tensor] = None, stream=None):
+    """transfer_ws for a small batch in one launch with no workspace (rpt_bf_transfer): the chain over rows 0..n-1 or
+    row_sel[0..n) and the insert of its survivors into every dst_filters[j] on dst_columns[j] in the same kernel; a
+    whole forward step of predicate transfer for one vector. n at most RPT_SMALL_PROBE_ROWS; out_sel must not overlap
+    row_sel. Arguments and result as transfer_ws; with the caller's out_sel and out_count nothing is allocated, read
+    back or synchronized."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    check(lib.rpt_bf_transfer(handles, arr, len(filters), dst_handles, darr, len(dst_filters), _ptr(row_sel), n,
+                              out_sel.data_ptr(), out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_range(filters, columns, dst_filters, dst_columns, *, range_mask, row_sel: Optional[torch.Tensor] = None,
+                   n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+                   out_count: Optional[torch.Tensor] = None, stream=None):
+    """transfer with the flagged filters' range tests, in one launch (rpt_bf_transfer_range); range_mask as in
+    probe_chain_range_ws (0: transfer itself), everything else as transfer."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    lib, device, handles, arr, n, out_sel, out_count = _probed_call_args(filters, columns, row_sel, n, out_sel, out_count)
+    mask = _range_mask_of(range_mask, len(filters))
+    check(lib.rpt_bf_transfer_range(handles, arr, len(filters), mask, dst_handles, darr, len(dst_filters),
+                                    _ptr(row_sel), n, out_sel.data_ptr(), out_count.data_ptr(),
+                                    _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def insert_multi(dst_filters, dst_columns, *, row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                 stream=None) -> None:
+    """The sink of one vector into one filter per build column, in one launch (rpt_bf_insert_multi): rows 0..n-1, or
+    row_sel[0..n), of every dst_columns[j] into dst_filters[j], as one insert per destination would leave them. n
+    (default: the length of row_sel, else of the first column) at most RPT_SMALL_PROBE_ROWS, 1..RPT_MAX_CHAIN
+    destinations. Columns as in probe_chain."""
+    dst_handles, darr = _dst_call_args(dst_filters, dst_columns)
+    n = _row_list_rows(dst_columns, row_sel, n)
+    lib, device = dst_filters[0]._lib, dst_filters[0].device
+    check(lib.rpt_bf_insert_multi(dst_handles, darr, len(dst_filters), _ptr(row_sel), n, _stream(device, stream)), lib)
 
 
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,

@@ -623,7 +623,7 @@ int rpt_bf_transfer_sel(const rpt_bf* const* filters, const rpt_key_column* cols
  *   rpt_bf_probe_chain_range (the row-list form: row_sel / n as in rpt_bf_probe_chain, n <= RPT_SMALL_PROBE_ROWS): one
  *   launch of one workgroup, no workspace. A (filter, 512-position segment) item of a flagged filter loads its keys
  *   once and computes range pass and hash from that load; a row outside the range makes no filter gather. Items of
- *   unflagged filters are the twin's. There is no one-launch row-list transfer.
+ *   unflagged filters are the twin's. The one-launch row-list transfer is rpt_bf_transfer_range, below.
  *
  * When to use them (measured on an MI355X, int64 keys, filter 0 flagged, its range covering 100 / 50 / 5 % of the probed
  *   keys, about 0.9 of the rows passing each Bloom test; DESIGN §5 "Ranges in the device-counted probes"):
@@ -670,6 +670,77 @@ int rpt_bf_transfer_sel_range(const rpt_bf* const* filters, const rpt_key_column
 int rpt_bf_probe_chain_range(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
                              uint32_t range_mask, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
                              uint64_t* out_count_dev, rpt_stream_t stream);
+
+/* The forward step and the sink of one vector in one launch. rpt_bf_transfer and rpt_bf_transfer_range are
+ * rpt_bf_transfer_ws / rpt_bf_transfer_range_ws without `workspace, workspace_bytes`: scan -> USE_BF chain -> CREATE_BF
+ * sink over a host-counted row list, one launch of one workgroup with no workspace, for n <= RPT_SMALL_PROBE_ROWS.
+ * rpt_bf_insert_multi is the sink alone: one vector into one filter per build column, in one launch. With
+ * rpt_bf_transfer_sel / rpt_bf_transfer_sel_range for the backward steps, every per-vector step of a forward-and-backward
+ * schedule is one kernel (and one node of a captured graph).
+ *
+ * Result (the transfers): exactly the _ws twin's for the same arguments. out_sel receives row_sel[i] (or i), in position
+ *   order, for every position i < n that passes the range test of every flagged filter on its own column and the Bloom
+ *   test of every filters[f] on cols[f]; *out_count_dev their number. Each dst_filters[j] ends bit-identical to
+ *   rpt_bf_insert of exactly those rows of dst_cols[j], ORed into what it holds, the min/max of the selected valid
+ *   I32/I64 keys folded in, a selected NULL row inserting NULL_HASH. row_sel may be null, ascending, or in any order with
+ *   repeats: a repeated row is probed, written and inserted as often as it is listed. Nothing at or past the returned
+ *   count is written to out_sel (exactly n entries are enough) and no row_sel entry at or past n is read. has_data
+ *   becomes 1 whenever n > 0. A destination may be listed twice, with different columns. range_mask == 0 in
+ *   rpt_bf_transfer_range hands over to rpt_bf_transfer, whose kernel is what runs and what the profiler records. The
+ *   range is read from device memory when the kernel runs: a captured call sees at every replay the min/max the filter
+ *   holds by then.
+ * Memory: key, validity, key_sel, row_sel and the output buffers (out_sel, the count) may be device-mapped pinned host
+ *   memory (hipHostGetDevicePointer), as for rpt_bf_probe_chain; the filters' words stay in device memory.
+ * Strategy: every probed filter is gathered and every insert is one atomic OR per row: forced probe and insert
+ *   strategies do not matter, and any filter size works.
+ * Argument checks, all before any launch and all RPT_ERR_INVALID_ARGUMENT. Before any handle is looked into: null lists
+ *   ("null argument"), n_filters / n_dst outside 1..RPT_MAX_CHAIN, a null handle, a destination that is also probed; the
+ *   mask (a bit at or above n_filters, a flagged HASH column) and the probed columns; n > RPT_SMALL_PROBE_ROWS ("n=...
+ *   rows exceeds RPT_SMALL_PROBE_ROWS", 2^32 and more included, before row_sel and out_sel are looked at); with a
+ *   row_sel, an out_sel range of n entries that overlaps row_sel's ("out_sel overlaps row_sel": the inserts read
+ *   row_sel after the tail has begun to write out_sel). Then, in rpt_bf_probe_chain_range's order: filters on different
+ *   devices; a destination off the chain's device or with a bad column; n == 0 sets *out_count_dev to 0, stream-ordered,
+ *   and touches no destination; a null out_sel; the destinations' capture and in-flight refusals; the probed filters'
+ *   pending clears settled (refused inside a capture).
+ * Ordering and capture: rpt_bf_transfer_sel's rules. Fully stream-ordered: no synchronisation, no copy, no allocation.
+ *   Every destination follows rpt_bf_insert's write rules (a deferred clear or an earlier write in flight is refused
+ *   inside a capture, otherwise the call is ordered after the destination's previous write and settles its clear); the
+ *   write scopes are taken in ascending handle address, a filter listed twice once, and held across the one launch, so
+ *   threads that list the same destinations in different orders do not deadlock.
+ *
+ * rpt_bf_insert_multi: the sink of one vector into 1..RPT_MAX_CHAIN filters in one launch. Each dst_filters[j] ends
+ *   bit-identical to rpt_bf_insert(dst_filters[j], &dst_cols[j], n) over rows 0..n-1, or over row_sel[0..n), min/max
+ *   included. n == 0 is a no-op and leaves has_data alone; otherwise has_data becomes 1. Refused before any handle is
+ *   looked into: null lists, n_dst outside 1..RPT_MAX_CHAIN ("n_dst=... outside 1..8"), a null destination handle,
+ *   n > RPT_SMALL_PROBE_ROWS. Then every destination must be on dst_filters[0]'s device and have a good column; then the
+ *   write rules and scopes of the transfer. The buffers may be device-mapped pinned host memory too.
+ *
+ * When to use them (measured on an MI355X, int64 keys, row_sel null, against rpt_bf_transfer_ws with the same arguments,
+ *   whose small-batch hand-over is already 1 + n_dst launches, and against the host loop "rpt_bf_probe_chain,
+ *   synchronize, read the count, one rpt_bf_insert_sel per destination"; 1 / 3 / 8 filters of 128 KiB or 16 MiB, 1-2
+ *   destinations, 0.1-0.9 of the rows surviving; spread within a line at most 4 %; DESIGN §5 "One launch for a forward
+ *   step"): at n = 2048 rpt_bf_transfer is level with or ahead of the _ws call in every shape, 1.00-1.16x faster per step
+ *   enqueued eagerly and 1.04-1.29x replayed from a graph, and 1.7-3.4x faster than the host loop. At 8192 rows it is
+ *   level or ahead (1.00-1.10x) while at most half of the rows survive and BEHIND when 0.9 survive (the _ws call is
+ *   1.04-1.25x faster). At 16384 rows it LOSES in 33 of 36 shapes: the _ws call is up to 1.6x faster (level only with
+ *   0.1 surviving), and with 0.9 surviving into two destinations even the host loop is 1-8 % faster. The filter size
+ *   hardly moves these ratios: one workgroup inserts the destinations one after another on one CU.
+ *   rpt_bf_insert_multi against one rpt_bf_insert per filter (1 / 2 / 4 filters): level at 2048 rows (0.90-1.05x eager;
+ *   replayed 0.85-0.97x for one filter, 1.04-1.10x for two and four), and it LOSES beyond: the m multi-workgroup inserts
+ *   are 2.1-2.2x faster at 8192 rows and 3.1-3.6x at 16384. So: one DuckDB vector (2048 rows) per call takes these
+ *   calls, for a modest gain and one graph node per step; row lists of 8192 and more take rpt_bf_transfer_ws /
+ *   rpt_bf_insert.
+ *   Nothing is dispatched on any of this: rpt_bf_transfer_ws keeps its hand-over and the caller picks the call. */
+int rpt_bf_transfer(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                    rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                    const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                    rpt_stream_t stream);
+int rpt_bf_transfer_range(const rpt_bf* const* filters, const rpt_key_column* cols, uint32_t n_filters,
+                          uint32_t range_mask, rpt_bf* const* dst_filters, const rpt_key_column* dst_cols,
+                          uint32_t n_dst, const uint32_t* row_sel, uint64_t n, uint32_t* out_sel,
+                          uint64_t* out_count_dev, rpt_stream_t stream);
+int rpt_bf_insert_multi(rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
+                        const uint32_t* row_sel, uint64_t n, rpt_stream_t stream);
 
 /* ---- merge / fold / export ----------------------------------------------------------------- */
 /* dst |= src (same log_num_blocks, same device): merging per-thread or per-GPU partial filters
