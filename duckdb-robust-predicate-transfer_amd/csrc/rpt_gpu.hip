@@ -58,6 +58,7 @@
 #include "kernels/range.hpp"
 #include "kernels/probe_sel_range.hpp"
 #include "kernels/transfer_small.hpp"
+#include "kernels/composite.hpp"
 
 // Host-side tuning macros (the kernels' own are in kernels/*.hpp).
 #ifndef RPT_LDS_HYBRID_MAX_LOG
@@ -1862,6 +1863,7 @@ int rpt_bf_transfer_insert_ws(const rpt_bf* const* filters, const rpt_key_column
 #include "rpt_probe_range.hpp"  // the min/max range stage: rpt_bf_range_bits and the range variants of the chain and transfers
 #include "rpt_probe_sel_range.hpp"  // ... of the device-counted probes and of the one-launch chains
 #include "rpt_transfer_small.hpp"  // the one-launch row-list transfer and the multi-filter sink of one vector
+#include "rpt_composite.hpp"  // composite join keys hashed inside the kernels
 
 
 int rpt_hash_combine(const rpt_key_column* col, uint64_t n, uint64_t* inout_hashes, rpt_stream_t stream) {

@@ -55,6 +55,12 @@ class KeyColumn(ctypes.Structure):
     ]
 
 
+class CompositeKey(ctypes.Structure):
+    """rpt_composite_key (include/rpt_gpu.h): a host array of n_cols KeyColumn descriptors."""
+
+    _fields_ = [("cols", POINTER(KeyColumn)), ("n_cols", c_uint32)]
+
+
 class BfInfo(ctypes.Structure):
     """rpt_bf_info (include/rpt_gpu.h)."""
 
@@ -218,6 +224,17 @@ SIGNATURES = {
          c_void_p, c_void_p, c_void_p],
     ),
     "rpt_bf_insert_multi": (c_int, [c_void_p, POINTER(KeyColumn), c_uint32, c_void_p, c_uint64, c_void_p]),
+    "rpt_hash_keys_composite": (c_int, [POINTER(CompositeKey), c_uint64, c_void_p, c_void_p]),
+    "rpt_bf_insert_composite": (c_int, [c_void_p, POINTER(CompositeKey), c_uint64, c_void_p]),
+    "rpt_bf_probe_chain_composite": (
+        c_int, [c_void_p, POINTER(CompositeKey), c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
+    ),
+    "rpt_bf_transfer_composite": (
+        c_int,
+        [c_void_p, POINTER(CompositeKey), c_uint32, c_void_p, POINTER(CompositeKey), c_uint32, c_void_p, c_uint64,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "rpt_bf_insert_multi_composite": (c_int, [c_void_p, POINTER(CompositeKey), c_uint32, c_void_p, c_uint64, c_void_p]),
     "rpt_bf_probe_phase1": (
         c_int, [c_void_p, POINTER(KeyColumn), c_void_p, c_uint64, c_void_p, c_size_t, c_void_p]
     ),

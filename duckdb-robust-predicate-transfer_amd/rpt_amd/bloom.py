@@ -21,6 +21,7 @@ from ._lib import (
     RPT_KEY_I32,
     RPT_KEY_I64,
     BfInfo,
+    CompositeKey,
     KeyColumn,
     RptError,
     check,
@@ -516,6 +517,79 @@ def insert_multi(dst_filters, dst_columns, *, row_sel: Optional[torch.Tensor] = 
     check(lib.rpt_bf_insert_multi(dst_handles, darr, len(dst_filters), _ptr(row_sel), n, _stream(device, stream)), lib)
 
 
+def _column_rows(c) -> int:
+    c = c if isinstance(c, dict) else {"keys": c}
+    return c["key_sel"].numel() if c.get("key_sel") is not None else c["keys"].numel()
+
+
+def composite_key(columns: Sequence) -> CompositeKey:
+    """rpt_composite_key of one key's columns: device key tensors, or dicts of make_column's arguments (keys, key_type,
+    key_sel, validity), the shape hash_columns accepts. The returned structure keeps its column array alive (the
+    tensors stay the caller's to keep)."""
+    if not columns:
+        raise RptError(1, "a composite key needs at least one column")
+    arr = (KeyColumn * len(columns))(*[make_column(**c) if isinstance(c, dict) else make_column(c) for c in columns])
+    key = CompositeKey(arr, len(columns))
+    key._columns = arr
+    return key
+
+
+def _composite_list_args(filters, keys, message: str):
+    """(handle array, rpt_composite_key array) of a filter list and one list of columns per filter."""
+    _check_lists(filters, keys, message)
+    built = [composite_key(k) for k in keys]
+    arr = (CompositeKey * len(built))(*built)
+    arr._keys = built  # the column arrays the structures point to
+    return (ctypes.c_void_p * len(filters))(*[f._h for f in filters]), arr
+
+
+def probe_chain_composite(filters, keys, *, row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                          out_sel: Optional[torch.Tensor] = None, out_count: Optional[torch.Tensor] = None,
+                          stream=None):
+    """probe_chain with a composite key per filter, hashed in the kernel (rpt_bf_probe_chain_composite): keys[i] is the
+    list of filters[i]'s key columns (tensors or make_column dicts, 1..RPT_MAX_KEY_COLUMNS, at most
+    RPT_MAX_CHAIN_KEY_COLUMNS over the call). Returns (out_sel, out_count); with the caller's buffers nothing is
+    allocated, read back or synchronized."""
+    handles, arr = _composite_list_args(filters, keys, "one key per filter, at least one filter")
+    n = _row_list_rows(keys[0], row_sel, n)
+    lib, device = filters[0]._lib, filters[0].device
+    if out_sel is None:
+        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    if out_count is None:
+        out_count = torch.zeros(1, dtype=torch.int64, device=device)
+    check(lib.rpt_bf_probe_chain_composite(handles, arr, len(filters), _ptr(row_sel), n, out_sel.data_ptr(),
+                                           out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def transfer_composite(filters, keys, dst_filters, dst_keys, *, row_sel: Optional[torch.Tensor] = None,
+                       n: Optional[int] = None, out_sel: Optional[torch.Tensor] = None,
+                       out_count: Optional[torch.Tensor] = None, stream=None):
+    """transfer with a composite key per probed filter and per destination (rpt_bf_transfer_composite); a destination
+    key of two or more columns folds no min/max. Arguments as probe_chain_composite, result as transfer."""
+    dst_handles, darr = _composite_list_args(dst_filters, dst_keys, "one key per destination filter, at least one destination")
+    handles, arr = _composite_list_args(filters, keys, "one key per filter, at least one filter")
+    n = _row_list_rows(keys[0], row_sel, n)
+    lib, device = filters[0]._lib, filters[0].device
+    if out_sel is None:
+        out_sel = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    if out_count is None:
+        out_count = torch.zeros(1, dtype=torch.int64, device=device)
+    check(lib.rpt_bf_transfer_composite(handles, arr, len(filters), dst_handles, darr, len(dst_filters), _ptr(row_sel), n,
+                                        out_sel.data_ptr(), out_count.data_ptr(), _stream(device, stream)), lib)
+    return out_sel, out_count
+
+
+def insert_multi_composite(dst_filters, dst_keys, *, row_sel: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                           stream=None) -> None:
+    """insert_multi with a composite key per destination (rpt_bf_insert_multi_composite)."""
+    dst_handles, darr = _composite_list_args(dst_filters, dst_keys, "one key per destination filter, at least one destination")
+    n = _row_list_rows(dst_keys[0], row_sel, n)
+    lib, device = dst_filters[0]._lib, dst_filters[0].device
+    check(lib.rpt_bf_insert_multi_composite(dst_handles, darr, len(dst_filters), _ptr(row_sel), n,
+                                            _stream(device, stream)), lib)
+
+
 def make_column(keys: torch.Tensor, key_type: Optional[int] = None, key_sel: Optional[torch.Tensor] = None,
                 validity: Optional[torch.Tensor] = None) -> KeyColumn:
     """rpt_key_column for a FLAT (key_sel None) or DICTIONARY (key_sel uint32/int32) key vector."""
@@ -691,6 +765,14 @@ class BloomFilter:
                                              _stream(self.device, stream)))
         else:
             check(self._lib.rpt_bf_insert(self._h, ctypes.byref(col), n, _stream(self.device, stream)))
+
+    def insert_composite(self, columns: Sequence, *, n: Optional[int] = None, stream=None) -> None:
+        """Insert rows 0..n-1 (default: the first column's length) of a composite key, hashed in the insert kernel
+        (rpt_bf_insert_composite): one atomic OR per row, no min/max for two or more columns. Columns as in
+        hash_columns."""
+        n = _column_rows(columns[0]) if n is None else int(n)
+        key = composite_key(columns)
+        check(self._lib.rpt_bf_insert_composite(self._h, ctypes.byref(key), n, _stream(self.device, stream)), self._lib)
 
     def insert_bits(self, keys: torch.Tensor, bits: torch.Tensor, *, n: Optional[int] = None,
                     row_sel: Optional[torch.Tensor] = None, key_type: Optional[int] = None, key_sel=None,
@@ -963,6 +1045,24 @@ def hash_columns(columns: Sequence, stream=None) -> torch.Tensor:
         col = make_column(c["keys"], c.get("key_type"), c.get("key_sel"), c.get("validity"))
         check(load().rpt_hash_combine(ctypes.byref(col), n, out.data_ptr(), _stream(out.device, stream)))
     return out
+
+
+def hash_columns_fused(columns: Sequence, stream=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hash_columns in one launch (rpt_hash_keys_composite): every column is read once and the combined hash written
+    once. Bit-identical to hash_columns; at most RPT_MAX_KEY_COLUMNS columns, a HASH column only first. `out`: the
+    caller's int64 buffer of at least n entries."""
+    if not columns:
+        raise RptError(1, "hash_columns_fused needs at least one column")
+    n = _column_rows(columns[0])
+    for c in columns[1:]:
+        if _column_rows(c) != n:
+            raise RptError(1, f"composite key columns differ in length ({_column_rows(c)} vs {n})")
+    key = composite_key(columns)
+    device = (columns[0]["keys"] if isinstance(columns[0], dict) else columns[0]).device
+    if out is None:
+        out = torch.empty(max(n, 1), dtype=torch.int64, device=device)
+    check(load().rpt_hash_keys_composite(ctypes.byref(key), n, out.data_ptr(), _stream(device, stream)))
+    return out[:n]
 
 
 def words_or_slices(dst: torch.Tensor, srcs: torch.Tensor, k: int, n_words: int, stream=None) -> None:

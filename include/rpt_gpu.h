@@ -742,6 +742,67 @@ int rpt_bf_transfer_range(const rpt_bf* const* filters, const rpt_key_column* co
 int rpt_bf_insert_multi(rpt_bf* const* dst_filters, const rpt_key_column* dst_cols, uint32_t n_dst,
                         const uint32_t* row_sel, uint64_t n, rpt_stream_t stream);
 
+/* ---- composite join keys, hashed inside the kernels ------------------------------------------ */
+/* A join key of several columns (the optimizer's multi-column transfer edges; HashColumns, reference
+ * src/bloom_filter.cpp:11-24) without the hash passes: the calls below read every column of a key once and hash and
+ * combine in the kernel that uses the hash, where rpt_hash_keys + rpt_hash_combine per further column write an 8-byte
+ * hash column to memory and read it back between the columns.
+ *
+ * A key, for every call below. Position i is row r = row_sel ? row_sel[i] : i. Column j contributes
+ *   Hash(keys_j[key_sel_j ? key_sel_j[r] : r]), or NULL_HASH where that physical index is NULL in validity_j, exactly as
+ *   rpt_hash_combine treats it; h = contrib_0, then h = CombineHashScalar(h, contrib_j) for j = 1 .. n_cols - 1. The
+ *   result is bit-identical to rpt_hash_keys(col_0) followed by rpt_hash_combine(col_j).
+ * Key types: RPT_KEY_I64 and RPT_KEY_I32, mixed freely. RPT_KEY_HASH only as column 0: a prefix already hashed, so a key
+ *   of more than RPT_MAX_KEY_COLUMNS columns is hashed in rounds; with n_cols == 1 it is the pre-hashed column of the
+ *   single-column calls. A HASH column at position >= 1 is RPT_ERR_INVALID_ARGUMENT.
+ * Min/max: a key of two or more columns folds no min/max into a destination filter (composite keys carry none); a key
+ *   of one column behaves exactly as in the single-column call, min/max included.
+ * Argument checks, before any handle is looked into and all RPT_ERR_INVALID_ARGUMENT: a null key or key list, null
+ *   cols ("null cols"), n_cols outside 1..RPT_MAX_KEY_COLUMNS ("n_cols=... outside 1..4"), a bad key type, a HASH column
+ *   past column 0 ("HASH column at position ..."), a null keys pointer, and for the one-launch calls more than
+ *   RPT_MAX_CHAIN_KEY_COLUMNS columns over the probed keys, or over the destination keys ("... columns over the ...
+ *   keys exceed RPT_MAX_CHAIN_KEY_COLUMNS"). The list checks a key check depends on (a null list, n_filters / n_dst
+ *   outside 1..RPT_MAX_CHAIN) come before it, the twin's other checks after it, in the twin's order.
+ *
+ * rpt_hash_keys_composite: out_hashes[i] for rows 0..n-1, any n, one launch; out_hashes holds exactly n entries.
+ *   n_cols == 1 forwards to rpt_hash_keys. Runs on the current device, like rpt_hash_keys.
+ * rpt_bf_insert_composite: rows 0..n-1 into bf, any n, one launch, one atomic OR per row. Every rule of rpt_bf_insert:
+ *   the write order, the deferred clear, capture, has_data; n == 0 is a no-op. n_cols == 1 forwards to rpt_bf_insert.
+ *   There is no routed (PARTITIONED / BUCKETED) composite insert: hash with rpt_hash_keys_composite and call
+ *   rpt_bf_insert_ws on the HASH column.
+ * rpt_bf_probe_chain_composite, rpt_bf_transfer_composite, rpt_bf_insert_multi_composite: rpt_bf_probe_chain,
+ *   rpt_bf_transfer and rpt_bf_insert_multi with a key per filter instead of a column: n <= RPT_SMALL_PROBE_ROWS, one
+ *   workgroup, one launch, no workspace, 1..RPT_MAX_CHAIN filters and destinations, and the twins' refusals before any
+ *   launch (filters on different devices, a destination among the probed filters, out_sel overlapping a given row_sel,
+ *   null arguments, n too large, captured destinations, pending clears). n == 0 sets the count to 0 and touches no
+ *   destination. The row_sel of the call is read once per (filter, 512-position segment), not once per column. With
+ *   every key of one column the result equals the single-column twin's: words, min/max, selection and count.
+ * When to use them (measured on an MI355X against the hash passes followed by the single-column call, int64 and int32
+ *   columns, row_sel null; DESIGN §5 "Composite keys hashed in the kernel"): one vector of 2048-8192 rows through 1 or 3
+ *   filters with keys of 2 or 3 columns is 1.1-3.5x faster per step enqueued eagerly and 1.1-2.1x replayed from a graph,
+ *   in every shape; at 16384 rows the calls are level with the passes (0.96-1.25x: behind by up to 4 % on 16 MiB filters
+ *   with three-column keys). rpt_hash_keys_composite is 1.25-2.7x faster (at 2^27 rows the ratio of the bytes moved),
+ *   rpt_bf_insert_composite 1.14-1.33x (the atomics bound both routes).
+ * Not provided: a composite form of the workspace chains (*_ws), of the device-counted *_sel calls, and of the range
+ *   mask (a range belongs to one column's values). Nothing dispatches to these calls. */
+#define RPT_MAX_KEY_COLUMNS 4        /* columns of one composite key */
+#define RPT_MAX_CHAIN_KEY_COLUMNS 16 /* columns over all probed keys of one call; likewise over all destination keys */
+typedef struct rpt_composite_key {
+  const rpt_key_column* cols; /* host array of n_cols column descriptors (device pointers inside, as everywhere) */
+  uint32_t n_cols;            /* 1..RPT_MAX_KEY_COLUMNS */
+} rpt_composite_key;
+int rpt_hash_keys_composite(const rpt_composite_key* key, uint64_t n, uint64_t* out_hashes, rpt_stream_t stream);
+int rpt_bf_insert_composite(rpt_bf* bf, const rpt_composite_key* key, uint64_t n, rpt_stream_t stream);
+int rpt_bf_probe_chain_composite(const rpt_bf* const* filters, const rpt_composite_key* keys, uint32_t n_filters,
+                                 const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                                 rpt_stream_t stream);
+int rpt_bf_transfer_composite(const rpt_bf* const* filters, const rpt_composite_key* keys, uint32_t n_filters,
+                              rpt_bf* const* dst_filters, const rpt_composite_key* dst_keys, uint32_t n_dst,
+                              const uint32_t* row_sel, uint64_t n, uint32_t* out_sel, uint64_t* out_count_dev,
+                              rpt_stream_t stream);
+int rpt_bf_insert_multi_composite(rpt_bf* const* dst_filters, const rpt_composite_key* dst_keys, uint32_t n_dst,
+                                  const uint32_t* row_sel, uint64_t n, rpt_stream_t stream);
+
 /* ---- merge / fold / export ----------------------------------------------------------------- */
 /* dst |= src (same log_num_blocks, same device): merging per-thread or per-GPU partial filters
  * built over disjoint row ranges gives the filter of the union, bit-identical to one build. */
